@@ -16,8 +16,15 @@ OpenAI server with SSE streaming.
 Rank 0 prints ONE JSON line; value = total output tokens/s over all ranks
 (time = max over ranks of the K timed waves, barrier + device sync on both sides).
 
-Second phase, ``tp_strong`` (BASELINE.json's "Llama-3-70B TP=8 over xGMI" config,
-VERDICT r2 next-round item 1): after the headline waves the SAME N ranks serve ONE
+A plain run does only that: set up, warm up, time ``--steps`` waves, print the line.
+Prompts and per-request sampling seeds come from fixed seeds, so the same arguments
+send the same requests in every run. ``--dump-outputs DIR`` also writes what the
+clients of the last timed wave received, as ``DIR/tokens.npy``: float32
+[requests, output tokens] token ids, -1 where a request got fewer tokens or a
+character that maps back to no id (``tokens_rank<r>.npy`` for ranks > 0).
+
+Second phase, ``tp_strong``, only with ``--full`` (BASELINE.json's "Llama-3-70B TP=8 over
+xGMI" config): after the headline waves the SAME N ranks serve ONE
 Llama-3-70B sharded TP=N (RCCL process group + the in-house IPC collectives), time
 boxed (``--tp-budget-s``, 150 s); its tok/s, p50 TTFT and ms/step go under the
 ``tp_strong`` key of the same JSON line, with the observed process-group backend /
@@ -70,9 +77,13 @@ def parse():
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: fp32 on the host with gloo collectives (tests of the DP / TP paths)")
     ap.add_argument("--num-kv-blocks", type=int, default=None, help="KV pool size (default: from HBM)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the tp_strong second phase")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the token ids the clients of the last timed wave received to DIR/tokens.npy")
     ap.add_argument("--tp-phase", choices=["auto", "on", "off"], default="auto",
-                    help="second phase: one --tp-model sharded over all N ranks (auto: on for the default "
-                         "GPU headline run)")
+                    help="with --full, the second phase: one --tp-model sharded over all N ranks (auto: on "
+                         "for the default GPU headline run)")
     ap.add_argument("--tp-model", default="llama-3-70b")
     ap.add_argument("--tp-steps", type=int, default=2)
     ap.add_argument("--tp-warmup", type=int, default=1)
@@ -82,7 +93,10 @@ def parse():
     ap.add_argument("--request-rate", type=float, default=None,
                     help="gateway path: open-loop Poisson arrivals at this rate (req/s) for the timed "
                          "region (steps x concurrency requests) instead of closed-loop waves")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.request_rate:
+        ap.error("--dump-outputs writes the last closed-loop wave: not available with --request-rate")
+    return args
 
 
 def _self_launch(args) -> int:
@@ -204,9 +218,9 @@ def orchestrate(args) -> int:
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    tp_phase = args.tp_phase == "on" or (
+    tp_phase = args.full and (args.tp_phase == "on" or (
         args.tp_phase == "auto" and args.device == "cuda" and args.tp == 1 and args.model == "llama-3-8b"
-        and not args.quantization and not args.request_rate)
+        and not args.quantization and not args.request_rate))
     dist = None
     ports = [_free_port(), _free_port()]
     # one directory shared by the node's ranks (single node: one rendezvous host), where
@@ -238,7 +252,7 @@ def orchestrate(args) -> int:
     if rc1 == 0 and tp_phase:
         t0 = time.time()
         argv2 = _strip(argv, {"--model", "--tp", "--steps", "--warmup", "--out", "--quantization",
-                              "--request-rate", "--tp-phase", "--num-kv-blocks"})
+                              "--request-rate", "--tp-phase", "--num-kv-blocks", "--dump-outputs"})
         argv2 += ["--model", args.tp_model, "--tp", str(world), "--steps", str(args.tp_steps),
                   "--warmup", str(args.tp_warmup), "--tp-phase", "off",
                   "--deadline", str(t0 + args.tp_budget_s - 15)]
@@ -287,6 +301,32 @@ def main():
     if not os.environ.get("HIPSERVE_BENCH_CHILD"):
         sys.exit(orchestrate(args))
     run_phase(args)
+
+
+def _ids_from_text(text, tokenizer):
+    """Token ids back from the text a client received. The synthetic tokenizer of the
+    random-init presets writes a token as `` w<id>`` or, for its 256 byte tokens, as the
+    raw byte: both map back, except a byte that did not decode as UTF-8 (-1). Digits that
+    make `` w<id>`` exceed the vocabulary are digit byte tokens that followed it. Any other
+    tokenizer: the text re-encoded."""
+    import re
+
+    from hipserve.tokenizer import SyntheticTokenizer
+
+    if not isinstance(tokenizer, SyntheticTokenizer):
+        return tokenizer.encode(text, add_special_tokens=False)
+    ids = []
+    for m in re.finditer(r" w(\d+)|(.)", text, re.S):
+        word, ch = m.groups()
+        if word is None:
+            ids.append(tokenizer.base + ord(ch) if ord(ch) < 128 else -1)
+            continue
+        k = len(word)
+        while k > 1 and int(word[:k]) >= tokenizer.vocab_size:
+            k -= 1
+        ids.append(int(word[:k]))
+        ids += [tokenizer.base + ord(c) for c in word[k:]]
+    return ids
 
 
 def run_phase(args):
@@ -375,24 +415,43 @@ def run_phase(args):
         threading.Thread(target=run_server, name="http", daemon=True).start()
         wait_http(f"http://127.0.0.1:{eport}/health", 120)
 
-        def wave():
+        def wave(keep=False):
+            # keep: the load generator holds on to the raw events of this wave (dump_outputs)
             res = lg.wave(url=stack.url, model=args.model, concurrency=args.concurrency,
                           input_len=args.input_len, output_len=args.output_len,
-                          vocab=min(V, 100000), temperature=args.temperature, top_p=args.top_p)
+                          vocab=min(V, 100000), temperature=args.temperature, top_p=args.top_p,
+                          seeded=True, keep=keep)
             return sum(r["tokens"] for r in res), [r["ttft"] for r in res]
     else:
-        def wave():
+        last_seqs = []
+
+        def wave(keep=False):
             prompts = [rng.integers(10, min(V, 100000), size=args.input_len).tolist()
                        for _ in range(args.concurrency)]
-            sp = SamplingParams(temperature=args.temperature, top_p=args.top_p,
-                                max_tokens=args.output_len, ignore_eos=True)
+            sps = [SamplingParams(temperature=args.temperature, top_p=args.top_p, max_tokens=args.output_len,
+                                  ignore_eos=True, seed=int(s))
+                   for s in rng.integers(0, 1 << 31, size=args.concurrency)]
             t_start = time.monotonic()
-            seqs = [engine.add_request(None, p, sp, arrival_time=t_start) for p in prompts]
+            seqs = [engine.add_request(None, p, sp, arrival_time=t_start) for p, sp in zip(prompts, sps)]
             ntok = 0
             while engine.has_unfinished():
                 for o in engine.step():
                     ntok += len(o.new_token_ids)
+            if keep:
+                last_seqs[:] = seqs
             return ntok, [s.first_token_time - s.arrival_time for s in seqs]
+
+    def dump_outputs():
+        """The token ids of the last timed wave, request by request, as float32 (exact below 2**24)."""
+        if args.path == "gateway":
+            rows = [_ids_from_text(t, engine.tokenizer) for t in lg.texts()]
+        else:
+            rows = [list(s.output_token_ids) for s in last_seqs]
+        arr = np.full((len(rows), max([args.output_len] + [len(r) for r in rows])), -1, dtype=np.float32)
+        for i, r in enumerate(rows):
+            arr[i, :len(r)] = r
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy" if rank == 0 else f"tokens_rank{rank}.npy"), arr)
 
     steps = args.steps
     t_w = time.perf_counter()
@@ -414,12 +473,14 @@ def run_phase(args):
 
         ol_summary = summarize(res, time.perf_counter() - t0)
     else:
-        for _ in range(steps):
-            n, tt = wave()
+        for i in range(steps):
+            n, tt = wave(keep=bool(args.dump_outputs) and i == steps - 1)
             tok_total += n
             ttfts += tt
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs()
 
     stats = torch.tensor([elapsed, float(tok_total)], dtype=torch.float64, device=dev)
     p50 = torch.tensor([statistics.median(ttfts)], dtype=torch.float64, device=dev)

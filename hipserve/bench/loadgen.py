@@ -30,10 +30,13 @@ def request_body(model, prompt, output_len, temperature, top_p, seed=None) -> by
 _JSON = {"Content-Type": "application/json"}
 
 
-async def one_request(session, url, model, prompt, output_len, temperature, top_p, seed=None, body=None):
+async def one_request(session, url, model, prompt, output_len, temperature, top_p, seed=None, body=None,
+                      keep=None):
     """One streaming completion; ``body`` = the pre-encoded request (a client
     has its request ready before the clock starts). Token events are counted
-    without decoding their JSON; only the final usage event is parsed."""
+    without decoding their JSON; only the final usage event is parsed. ``keep``: a
+    list that receives the raw token events (``event_text`` decodes them later,
+    outside the timed wave)."""
     if body is None:
         body = request_body(model, prompt, output_len, temperature, top_p, seed)
     t0 = time.perf_counter()
@@ -69,8 +72,15 @@ async def one_request(session, url, model, prompt, output_len, temperature, top_
                     itls.append(now - last)
                 last = now
                 ntok += 1
+                if keep is not None:
+                    keep.append(ev)
     n = usage["completion_tokens"] if usage else ntok
     return {"ttft": ttft, "tokens": n, "latency": time.perf_counter() - t0, "itl": itls}
+
+
+def event_text(events) -> str:
+    """The text a client received in one stream: its token events' ``text`` fields, in order."""
+    return "".join(c.get("text") or "" for ev in events for c in json.loads(ev[6:]).get("choices", ()))
 
 
 def make_prompts(rng: random.Random, concurrency: int, input_len: int, vocab: int) -> list[list[int]]:
@@ -82,7 +92,8 @@ def make_prompts(rng: random.Random, concurrency: int, input_len: int, vocab: in
 
 
 async def wave(url, model, concurrency, input_len, output_len, vocab, temperature=0.8, top_p=0.95,
-               rng=None, session=None, prompts=None, bodies=None):
+               rng=None, session=None, prompts=None, bodies=None, keep=None):
+    """``keep``: a list that receives one list of raw token events per request, in request order."""
     rng = rng or random.Random(0)
     if prompts is None and bodies is None:
         prompts = make_prompts(rng, concurrency, input_len, vocab)
@@ -92,9 +103,12 @@ async def wave(url, model, concurrency, input_len, output_len, vocab, temperatur
     if own:
         session = aiohttp.ClientSession(timeout=aiohttp.ClientTimeout(total=None),
                                         connector=aiohttp.TCPConnector(limit=0))
+    if keep is not None:
+        keep[:] = [[] for _ in bodies]
     try:
         res = await asyncio.gather(*[one_request(session, url, model, None, output_len, temperature, top_p,
-                                                 body=b) for b in bodies])
+                                                 body=b, keep=None if keep is None else keep[i])
+                                     for i, b in enumerate(bodies)])
     finally:
         if own:
             await session.close()
@@ -196,8 +210,12 @@ def main(argv=None):
 
 
 def _bodies(rng, key):
-    model, conc, inp, out, vocab, temp, top_p = key
-    return [request_body(model, p, out, temp, top_p) for p in make_prompts(rng, conc, inp, vocab)]
+    """One wave's requests. ``seeded``: every request carries its own sampling seed drawn
+    from ``rng``, so the same command sequence asks for the same samples in every run."""
+    model, conc, inp, out, vocab, temp, top_p, seeded = key
+    prompts = make_prompts(rng, conc, inp, vocab)
+    seeds = [rng.getrandbits(31) if seeded else None for _ in prompts]
+    return [request_body(model, p, out, temp, top_p, seed=s) for p, s in zip(prompts, seeds)]
 
 
 def serve_stdio():
@@ -208,6 +226,7 @@ def serve_stdio():
     loop = asyncio.new_event_loop()
     session = None
     rng = random.Random(1234)
+    kept = None  # raw token events of the last wave sent with "keep"
     pending = None  # (shape key, prompts) of the NEXT wave, generated while idle:
     # a client has its prompts ready; building them is not part of the timed wave
     for line in sys.stdin:
@@ -231,16 +250,21 @@ def serve_stdio():
             sys.stdout.write(json.dumps(out) + "\n")
             sys.stdout.flush()
             continue
+        if cmd["op"] == "texts":  # what each request of the last ``keep`` wave received
+            sys.stdout.write(json.dumps({"ok": True, "texts": [event_text(evs) for evs in kept or []]}) + "\n")
+            sys.stdout.flush()
+            continue
         if cmd["op"] == "wave":
             key = (cmd["model"], cmd["concurrency"], cmd["input_len"], cmd["output_len"], cmd["vocab"],
-                   cmd.get("temperature", 0.8), cmd.get("top_p", 0.95))
+                   cmd.get("temperature", 0.8), cmd.get("top_p", 0.95), bool(cmd.get("seeded")))
             bodies = pending[1] if pending is not None and pending[0] == key else _bodies(rng, key)
+            kept = [] if cmd.get("keep") else None
             t0 = time.perf_counter()
             try:
                 res = loop.run_until_complete(wave(cmd["url"], cmd["model"], cmd["concurrency"],
                                                    cmd["input_len"], cmd["output_len"], cmd["vocab"],
                                                    cmd.get("temperature", 0.8), cmd.get("top_p", 0.95),
-                                                   rng=rng, session=session, bodies=bodies))
+                                                   rng=rng, session=session, bodies=bodies, keep=kept))
                 out = {"ok": True, "results": res, "elapsed": time.perf_counter() - t0}
             except Exception as e:
                 out = {"ok": False, "error": repr(e)}

@@ -159,6 +159,14 @@ class LoadgenProc:
             raise RuntimeError(out["error"])
         return out["results"]
 
+    def texts(self):
+        """The text each request of the last ``wave(keep=True)`` received, in request order."""
+        import json
+
+        self.p.stdin.write('{"op": "texts"}\n')
+        self.p.stdin.flush()
+        return json.loads(self.p.stdout.readline() or '{"texts": []}')["texts"]
+
     def open_loop(self, **kw):
         """Open-loop arrivals (loadgen.open_loop); returns (results, elapsed_s)."""
         import json

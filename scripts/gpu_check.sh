@@ -37,7 +37,7 @@ run_ops() {
   local rc=$?; cat $OUT/bench_ops.log; return $rc
 }
 run_bench() {
-  timeout -k 10 480 python -u bench.py --out $OUT/bench.json > $OUT/bench.log 2>&1
+  timeout -k 10 480 python -u bench.py --full --out $OUT/bench.json > $OUT/bench.log 2>&1
   local rc=$?; tail -n 2 $OUT/bench.log; return $rc
 }
 run_bench_q4() {

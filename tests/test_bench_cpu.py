@@ -87,7 +87,7 @@ def test_bench_tp_strong_phase(n):
     strong-scaling point) and reports it under ``tp_strong`` in the SAME JSON
     line, with the observed process-group backend / world size and the custom
     all-reduce state. Here: gloo, CPU-sized model with 8 kv heads."""
-    out = _run(_torchrun(n, 29670 + n, ARGS + ["--tp-phase", "on", "--tp-model", "tiny-llama-tp8"]))
+    out = _run(_torchrun(n, 29670 + n, ARGS + ["--full", "--tp-phase", "on", "--tp-model", "tiny-llama-tp8"]))
     assert out["n_gpus"] == n and out["config"]["parallelism"] == f"dp{n}" and out["scaling"] == "weak"
     tp = out["tp_strong"]
     assert tp["status"] == "ok" and tp["model"] == "tiny-llama-tp8" and tp["tp"] == n
@@ -105,7 +105,7 @@ def test_bench_tp_strong_phase(n):
 def test_bench_tp_phase_time_box():
     """A TP phase that cannot finish in its budget is killed and reported, and the
     headline line is still printed (exit 0)."""
-    out = _run([sys.executable, "bench.py"] + ARGS + ["--tp-phase", "on", "--tp-model", "tiny-llama-tp8",
+    out = _run([sys.executable, "bench.py"] + ARGS + ["--full", "--tp-phase", "on", "--tp-model", "tiny-llama-tp8",
                                                        "--tp-budget-s", "0.5"])
     assert out["value"] > 0 and out["tp_strong"]["status"] == "timeout"
 
@@ -136,7 +136,7 @@ def test_bench_tp_strong_rank_failure_fails_fast():
     import time
 
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", HIPSERVE_FAULT="rank3:init@0")
-    cmd = _torchrun(8, 29690, ARGS + ["--tp-phase", "on", "--tp-model", "tiny-llama-tp8",
+    cmd = _torchrun(8, 29690, ARGS + ["--full", "--tp-phase", "on", "--tp-model", "tiny-llama-tp8",
                                       "--tp-budget-s", "600"])
     t0 = time.time()
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
@@ -149,3 +149,51 @@ def test_bench_tp_strong_rank_failure_fails_fast():
     assert lines[0]["value"] > 0  # the headline phase (no TP ranks) was unaffected
     assert tp["phase_wall_s"] < 30, tp  # every rank out within 30 s (3.5 s measured here)
     assert time.time() - t0 < 300
+
+
+def test_bench_plain_run_has_no_second_phase():
+    """Without --full a run is the headline phase alone, whatever --tp-phase says."""
+    out = _run([sys.executable, "bench.py"] + ARGS + ["--tp-phase", "on", "--tp-model", "tiny-llama-tp8"])
+    assert out["value"] > 0 and out["steps"] == 1 and "tp_strong" not in out
+
+
+def _dump(tmp_path, name, extra, lo=0):
+    import numpy as np
+
+    d = tmp_path / name
+    out = _run([sys.executable, "bench.py"] + ARGS + ["--steps", "2", "--dump-outputs", str(d)] + extra)
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert sorted(p.name for p in d.iterdir()) == ["tokens.npy"]
+    tok = np.load(d / "tokens.npy")
+    # one row per request of the last timed wave, one column per generated token
+    assert tok.dtype == np.float32 and tok.shape == (2, 4)
+    assert ((tok >= lo) & (tok < 512) & (tok == np.round(tok))).all()  # tiny-llama: vocabulary of 512
+    return tok
+
+
+def test_bench_dump_outputs_gateway(tmp_path):
+    """--dump-outputs through the gateway path: the ids are read back from the text the
+    load generator's clients received (-1: fewer tokens than asked for came back as text,
+    or a byte token that is no UTF-8 on its own; half of this tiny vocabulary is byte tokens)."""
+    _dump(tmp_path, "gw", [], lo=-1)
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """Same arguments, same prompts and sampling seeds: the engine path (requests added in
+    a fixed order) writes the same tokens in two runs."""
+    a = _dump(tmp_path, "a", ["--path", "engine"])
+    b = _dump(tmp_path, "b", ["--path", "engine"])
+    assert (a == b).all()
+
+
+def test_bench_ids_from_text_round_trip():
+    """The dump reads token ids back from the synthetic tokenizer's text: placeholder
+    words, ASCII byte tokens, and a digit byte token right after a word (the merged
+    number would exceed the vocabulary)."""
+    import bench
+    from hipserve.tokenizer import SyntheticTokenizer
+
+    tok = SyntheticTokenizer(512)
+    ids = [300, tok.base + ord("7"), 5, 511, tok.base + ord(" "), 400, tok.base + ord("a"), 259]
+    assert bench._ids_from_text(tok.decode(ids), tok) == ids
+    assert bench._ids_from_text(tok.decode([300, tok.base + 0xC3, 301]), tok) == [300, -1, 301]
