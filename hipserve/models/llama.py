@@ -6,11 +6,15 @@ their own RoPE bases) and Phi-3 — one parameterised model, the family switches
 are ``ModelConfig`` fields (the reference's chart defaults are Gemma-3, Qwen3-VL-MoE
 and Qwen3: vllm-models/helm-chart/values.yaml:1-19).
 
-Per layer: fused add+RMSNorm -> merged QKV GEMM (hipBLASLt) -> fused RoPE +
-paged-cache write -> paged attention (prefill and/or decode kernels) -> o_proj GEMM
--> TP all-reduce -> fused add+RMSNorm -> merged gate/up GEMM -> SiLU*up ->
-down GEMM -> TP all-reduce. Weights are held as plain tensors already laid out
-for the kernels ([out, in] row-major, TP-sharded on load), no nn.Module tracing.
+Per layer: merged QKV GEMM -> RoPE + paged-cache write -> paged attention (prefill
+and/or decode kernels) -> o_proj GEMM -> TP reduction + residual add + RMSNorm ->
+merged gate/up GEMM with the GLU (or the routed experts, models/moe.py) -> down GEMM
+-> TP reduction + residual add + the next layer's RMSNorm. ``forward`` runs prefill
+and mixed batches (packed-layout, GGUF-block, FP8 or hipBLASLt GEMMs per weight);
+``forward_decode_fused`` runs decode-only batches, the decode GEMMs' split-K partials
+reduced inside the op that consumes them. Weights are plain tensors ([out, in]
+row-major, TP-sharded on load), ``gemm.PackedLinear`` or quantised (ops/quant.py);
+no nn.Module tracing.
 
 The reference never contains model code — it runs `vllm/vllm-openai:v0.11.0`
 with `--tensor-parallel-size <gpuRequestCount>`
@@ -19,10 +23,9 @@ in-house replacement for that engine's model executor.
 """
 from __future__ import annotations
 
-import logging
 import math
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 
 import torch
 import torch.nn.functional as F
@@ -32,12 +35,7 @@ from ..ops import gemm, pgemm
 from ..ops import quant as Q
 from ..ops import reference as ref
 from ..parallel.comm import TPGroup
-
-log = logging.getLogger(__name__)
-
-DG_MOE_STEPS = (1, 2, 3, 4, 6, 7, 8, 16)  # 256-k steps per K slice the expert decode GEMM is built for
-MOE_KERNEL_MAX_PAIRS = 2048  # larger (prefill) batches use per-expert hipBLASLt GEMMs ...
-MOE_KERNEL_MAX_ROWS_PER_EXPERT = 1024  # ... unless the experts are many and small (Qwen3-MoE: 128 x 768)
+from .moe import MOE_KERNEL_MAX_PAIRS, MOE_KERNEL_MAX_ROWS_PER_EXPERT, MoEMixin  # noqa: F401 (re-exported)
 
 
 @dataclass
@@ -82,7 +80,6 @@ class LayerWeights:
     w13: torch.Tensor | None = None          # [E, 2*I/TP, H]
     w2: torch.Tensor | None = None           # [E, H, I/TP]
     moe_packed: tuple | None = None          # (w13 gate/up-interleaved, w2) packed per expert for decode
-    quant: dict = field(default_factory=dict)  # GGUF-quantized GEMM weights by name
     # family extras (Qwen2 bias, Qwen3/Gemma-3 per-head q/k norms, Gemma-3 sandwich norms)
     bqkv: torch.Tensor | None = None         # [(nq + 2 nkv) * D / TP]
     q_norm: torch.Tensor | None = None       # [D] fp32
@@ -107,7 +104,7 @@ def shard_sizes(cfg: ModelConfig, tp: int):
     return nq, nkv, inter, vpad
 
 
-class LlamaModel:
+class LlamaModel(MoEMixin):
     # load FP8 checkpoints natively (e4m3 + scales, ops/quant.py) instead of
     # dequantising them to bf16 at load (weights/safetensors_loader.py)
     native_fp8 = True
@@ -147,8 +144,6 @@ class LlamaModel:
         self.cos_sin_local = self.cos_sin
         if cfg.rope_local_theta and any(cfg.layer_windows):
             self.cos_sin_local = ref.rope_cos_sin(self.D, mp, cfg.rope_local_theta, None).to(self.device)
-        self.vanilla = not (cfg.qkv_bias or cfg.qk_norm or cfg.sandwich_norm or cfg.hidden_act != "silu"
-                            or any(cfg.layer_windows) or cfg.embed_scale != 1.0)
         # families the fused decode layer covers: Llama-style plus q/k/v bias (Qwen2),
         # per-head q/k RMSNorm (Qwen3; folded into the split-K RoPE epilogue), MoE MLPs
         # (Mixtral, Qwen3-MoE / Qwen3-VL-MoE) and Gemma-3 (sandwich norms in
@@ -249,7 +244,6 @@ class LlamaModel:
         dequantised to dense weights (CPU plumbing / numerics oracle)."""
         import numpy as np
 
-        from ..ops import quant as Q
         from ..weights import gguf as G
 
         if scheme.lower() in ("fp8", "int8"):
@@ -294,8 +288,6 @@ class LlamaModel:
         the quantised expert GEMM. Embeddings, norms, router and lm_head stay bf16 (the
         checkpoints' ``ignore`` list). Off the GPU the same 8-bit values are
         dequantised to dense weights."""
-        from ..ops import quant as Q
-
         self.allocate_random(seed=seed)  # norms, embeddings, lm_head, bf16 projections (replaced below)
         dev = self.device
 
@@ -345,11 +337,10 @@ class LlamaModel:
 
     def quant_moes(self) -> list:
         """Every quantised expert stack (QuantMoE)."""
-        from ..ops import quant as Q
         return [w for lw in self.layers for w in (lw.w13, lw.w2) if isinstance(w, Q.QuantMoE)]
 
     # ---------------------------------------------------------------- forward
-    def linear(self, x: torch.Tensor, w, name: str | None = None) -> torch.Tensor:
+    def linear(self, x: torch.Tensor, w) -> torch.Tensor:
         if isinstance(w, (torch.Tensor, gemm.PackedLinear)):
             return gemm.linear(x, w)
         return self.quant_linear(x, w)
@@ -446,45 +437,6 @@ class LlamaModel:
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
         return n, freed
-
-    def pack_moe_weights(self, drop_plain: bool = False) -> int:
-        """Per-expert packed copies of the MoE weights for the decode expert GEMM
-        (``moe_hip``): w13 gate/up-interleaved (SiLU-GLU in the GEMM epilogue), w2
-        plain. The row-major originals stay for prefill (per-expert hipBLASLt), so
-        this doubles the expert bytes (Mixtral-8x7B: +90 GB of 288 GB) — skipped
-        when less than 24 GiB of HBM would stay free for the KV cache, or with
-        HIPSERVE_MOE_PACK=0 (the row-major expert GEMM runs instead)."""
-        if (not self.cfg.num_experts or getattr(self.ops, "name", "") != "hip"
-                or os.environ.get("HIPSERVE_MOE_PACK", "1") == "0"):
-            return 0
-        lws = [lw for lw in self.layers if isinstance(lw.w13, torch.Tensor) and self._moe_decode_ok(lw)]
-        if not lws:
-            return 0
-        need = sum(2 * (lw.w13.numel() + lw.w2.numel()) for lw in lws)
-        if drop_plain:  # the packed copy REPLACES the row-major experts (one layer at a time)
-            if not all(lw.moe_packed is not None or self.cfg.hidden_act == "silu" for lw in lws):
-                return 0
-            need = 0
-        if self.device.type == "cuda":
-            free, _ = torch.cuda.mem_get_info(self.device)
-            if need + (24 << 30) > free:
-                log.warning("MoE decode weights not packed: %.1f GB needed, %.1f GB free", need / 2**30, free / 2**30)
-                return 0
-        op = torch.ops.hipserve
-        freed = 0
-        for lw in lws:
-            if lw.moe_packed is None:
-                E, N13, K13 = lw.w13.shape
-                _, N2, K2 = lw.w2.shape
-                p13 = torch.empty(E, N13 * K13, dtype=lw.w13.dtype, device=lw.w13.device)
-                p2 = torch.empty(E, -(-N2 // 128) * 128 * K2, dtype=lw.w2.dtype, device=lw.w2.device)
-                op.pack_decode_weight(p13, lw.w13.contiguous(), True)  # all experts in one launch
-                op.pack_decode_weight(p2, lw.w2.contiguous(), False)
-                lw.moe_packed = (p13, p2)
-            if drop_plain and self.moe_packed_prefill(lw, for_drop=True):
-                freed += 2 * (lw.w13.numel() + lw.w2.numel())
-                lw.w13 = lw.w2 = None
-        return freed if drop_plain else need
 
     def fused_gemm_shapes(self) -> dict:
         """{(N, K): epilogue spec} of the projections whose decode GEMM output feeds
@@ -608,18 +560,47 @@ class LlamaModel:
         h = h * mask.unsqueeze(-1).to(h.dtype)
         return self.tp.all_reduce(h)
 
+    def _embed(self, ids: torch.Tensor, meta: AttnMeta) -> torch.Tensor:
+        h = self.embed_tokens(self.resolve_ids(ids, meta))
+        if self.cfg.embed_scale != 1.0:  # Gemma: embeddings * sqrt(hidden), the scale rounded to the dtype
+            h = h * float(torch.tensor(self.cfg.embed_scale, dtype=h.dtype))
+        return h
+
+    def _rowpar_norm(self, xn, residual, x, w, post_w, next_w, x8, h=None, add=None):
+        """``forward``'s o_proj / down_proj tail: residual += x @ w.T summed over the TP
+        ranks (``post_w``: through Gemma's sandwich norm first), xn = RMSNorm(residual) *
+        next_w, also as e4m3 into ``x8`` (``_x8p``). ``h``: the projection's output where the
+        caller already has it (MoE, FP8 down); ``add`` = (rows, features): DeepStack."""
+        ops, eps, T = self.ops, self.cfg.rms_norm_eps, xn.shape[0]
+        if h is None and add is None and post_w is None and self.tp.world_size == 1:
+            # residual add in the GEMM's own epilogue: packed layout / GGUF blocks
+            epi = (gemm.packed_prefill if isinstance(w, gemm.PackedLinear) and T > 64
+                   else Q.qprefill if Q.qprefill_ok(w, T) else None)
+            if epi is not None:
+                epi(x, w, 1, out=residual)
+                return ops.rmsnorm(xn, residual, next_w, eps, out8=x8)
+        if h is None:
+            h = self.linear_rowpar(x, w)
+        if add is not None and self.tp.rank == 0:
+            # DeepStack: visual features join the residual stream after this layer
+            # (rank 0 only: the row-parallel partials are summed across ranks next)
+            h = h.index_add(0, add[0], add[1].to(h.dtype))
+        if post_w is not None:  # Gemma sandwich norm (after the TP reduction)
+            h = self._tp_sum(h, xn)
+            ops.rmsnorm(h, h, post_w, eps)
+            ops.fused_add_rmsnorm(xn, h, residual, next_w, eps, out8=x8)
+        else:
+            self.add_rmsnorm(xn, residual, h, 1, next_w, out8p=x8)
+
     def forward(self, ids: torch.Tensor, meta: AttnMeta, kv_caches) -> torch.Tensor:
         ops, cfg = self.ops, self.cfg
         T = ids.shape[0]
-        H, D, nq, nkv = cfg.hidden_size, self.D, self.nq, self.nkv
+        D, nq, nkv = self.D, self.nq, self.nkv
         eps = cfg.rms_norm_eps
         Tp, Td = meta.num_prefill_tokens, meta.num_decode
         if self._fused_ok(meta):
             return self.forward_decode_fused(ids, meta, kv_caches)
-        ids = self.resolve_ids(ids, meta)
-        h = self.embed_tokens(ids)
-        if cfg.embed_scale != 1.0:  # Gemma: embeddings * sqrt(hidden), the scale rounded to the dtype
-            h = h * float(torch.tensor(cfg.embed_scale, dtype=h.dtype))
+        h = self._embed(ids, meta)
         ds = None
         if meta.mm_rows is not None:  # image placeholders take the vision tower's embeddings
             h.index_copy_(0, meta.mm_rows, meta.mm_embeds.to(h.dtype))
@@ -633,7 +614,6 @@ class LlamaModel:
         x8 = self._x8p(xn, self.layers[0].wqkv)  # FP8 models: the norm writes the e4m3 GEMM input too
         ops.rmsnorm(xn, h, self.layers[0].ln1, eps, out8=x8)
         L = len(self.layers)
-        tp1 = self.tp.world_size == 1
         for i, lw in enumerate(self.layers):
             # prefill-sized batches: FP8 W8A8 (ops/pgemm.py), the packed-layout GEMM of a
             # single-layout model (gemm.linear dispatches PackedLinear), else hipBLASLt
@@ -656,64 +636,33 @@ class LlamaModel:
                 ops.paged_decode(attn[Tp:Tp + Td], qkv[Tp:Tp + Td], kc, vc, meta.bt_decode, meta.ctx_decode,
                                  tmp_out, tmp_ml, nq, nkv, part, self.scale, win)
             x8 = self._x8p(xn, lw.wgu, glu=True)
-            if tp1 and lw.post_attn_norm is None and isinstance(lw.wo, gemm.PackedLinear) and T > 64:
-                gemm.packed_prefill(attn, lw.wo, 1, out=residual)  # residual += o_proj(attn), packed layout
-                ops.rmsnorm(xn, residual, lw.ln2, eps, out8=x8)
-            elif tp1 and lw.post_attn_norm is None and Q.qprefill_ok(lw.wo, T):
-                Q.qprefill(attn, lw.wo, 1, out=residual)  # GGUF blocks, residual add in the epilogue
-                ops.rmsnorm(xn, residual, lw.ln2, eps, out8=x8)
-            else:
-                o = self.linear_rowpar(attn, lw.wo)
-                if lw.post_attn_norm is not None:  # Gemma sandwich norm (after the TP reduction)
-                    o = self._tp_sum(o, xn)
-                    ops.rmsnorm(o, o, lw.post_attn_norm, eps)
-                    ops.fused_add_rmsnorm(xn, o, residual, lw.ln2, eps, out8=x8)
-                else:
-                    self.add_rmsnorm(xn, residual, o, 1, lw.ln2, out8p=x8)
+            self._rowpar_norm(xn, residual, attn, lw.wo, lw.post_attn_norm, lw.ln2, x8)
             nxt = self.layers[i + 1].ln1 if i + 1 < L else self.norm
             x8n = self._x8p(xn, self.layers[i + 1].wqkv) if i + 1 < L else None  # next layer's qkv input
+            act = h = None  # the down projection's input, or its output where already computed
             if lw.router is not None:
                 h = self.moe(xn, lw)
             else:
                 gelu = cfg.hidden_act == "gelu_tanh"
-                act = act8 = None
                 if pgemm.f8_use(lw.wgu, T, glu=True):  # FP8 gate|up
+                    act8 = None
                     if pgemm.f8_use(lw.wd, T):  # FP8 down too: act straight to e4m3 (glu_quant)
                         act8 = pgemm.f8_glu_q8(xn, lw.wgu, gelu, x8)
-                    if act8 is None:  # GLU in the e4m3 GEMM's epilogue
+                    if act8 is not None:
+                        h = pgemm.f8_gemm(None, lw.wd, 0, x8=act8)
+                    else:  # GLU in the e4m3 GEMM's epilogue
                         act = pgemm.f8_gemm(xn, lw.wgu, 3 if gelu else 2, x8=x8)
                 elif isinstance(lw.wgu, gemm.PackedLinear) and lw.wgu.glu:  # GLU in the packed GEMM's epilogue
                     act = gemm.packed_glu(xn, lw.wgu, gelu)
                 elif cfg.hidden_act in ("silu", "gelu_tanh") and Q.qprefill_ok(lw.wgu, T, glu=True):
                     act = Q.qprefill(xn, lw.wgu, 3 if gelu else 2)  # GGUF blocks, GLU in the epilogue
-                if act8 is not None:
-                    h = pgemm.f8_gemm(None, lw.wd, 0, x8=act8)
-                elif act is None:
+                if act is None and h is None:
                     gu = self.linear(xn, lw.wgu)
                     act = torch.empty(T, self.inter, device=xn.device, dtype=xn.dtype)
                     self.act_and_mul(act, gu)
-                if act8 is None and (tp1 and lw.post_ff_norm is None and not (ds is not None and i < len(ds))
-                                     and (Q.qprefill_ok(lw.wd, T)
-                                          or (isinstance(lw.wd, gemm.PackedLinear) and T > 64))):
-                    if isinstance(lw.wd, gemm.PackedLinear):
-                        gemm.packed_prefill(act, lw.wd, 1, out=residual)
-                    else:
-                        Q.qprefill(act, lw.wd, 1, out=residual)
-                    ops.rmsnorm(xn, residual, nxt, eps, out8=x8n)
-                    x8 = x8n
-                    continue
-                if act8 is None:
-                    h = self.linear_rowpar(act, lw.wd)
-            if ds is not None and i < len(ds) and self.tp.rank == 0:
-                # DeepStack: visual features join the residual stream after layer i
-                # (rank 0 only: the row-parallel partials are summed across ranks next)
-                h = h.index_add(0, meta.mm_rows, ds[i].to(h.dtype))
-            if lw.post_ff_norm is not None:
-                h = self._tp_sum(h, xn)
-                ops.rmsnorm(h, h, lw.post_ff_norm, eps)
-                ops.fused_add_rmsnorm(xn, h, residual, nxt, eps, out8=x8n)
-            else:
-                self.add_rmsnorm(xn, residual, h, 1, nxt, out8p=x8n)
+            # DeepStack (Qwen3-VL): visual features join the residual stream after layers 0..n-1
+            add = (meta.mm_rows, ds[i]) if ds is not None and i < len(ds) else None
+            self._rowpar_norm(xn, residual, act, lw.wd, lw.post_ff_norm, nxt, x8n, h, add)
             x8 = x8n
         return xn
 
@@ -727,12 +676,11 @@ class LlamaModel:
     def forward_decode_fused(self, ids: torch.Tensor, meta: AttnMeta, kv_caches) -> torch.Tensor:
         """Decode-only forward with the decode GEMMs' split-K partials reduced
         inside the next op (at TP>1 the o_proj / down epilogues are the in-house
-        cross-rank reduce + residual + RMSNorm kernel, ``add_rmsnorm``): qkv -> RoPE + KV write, o_proj -> residual add + RMSNorm,
-        down -> residual add + the NEXT
-        layer's RMSNorm (final norm after the last layer), SiLU-GLU in the gate|up
-        GEMM's epilogue (gate/up-interleaved packing). Bit-identical to
-        ``forward``; each fusion point falls back to the unfused op when the tuner
-        picked hipBLASLt for that projection."""
+        cross-rank reduce + residual + RMSNorm kernel, ``add_rmsnorm``): qkv -> RoPE + KV
+        write, o_proj -> residual add + RMSNorm, down -> residual add + the NEXT layer's
+        RMSNorm (final norm after the last layer), SiLU-GLU in the gate|up GEMM's epilogue
+        (gate/up-interleaved packing). Bit-identical to ``forward``; each fusion point
+        falls back to the unfused op when the tuner picked hipBLASLt for that projection."""
         ops, cfg, op = self.ops, self.cfg, torch.ops.hipserve
         T = ids.shape[0]
         D, nq, nkv = self.D, self.nq, self.nkv
@@ -750,9 +698,7 @@ class LlamaModel:
                              *(xn8 if xn8 is not None else (None, None)))
             h = residual
         else:
-            h = self.embed_tokens(self.resolve_ids(ids, meta))
-            if cfg.embed_scale != 1.0:  # Gemma: as forward()
-                h = h * float(torch.tensor(cfg.embed_scale, dtype=h.dtype))
+            h = self._embed(ids, meta)
             residual = h.clone()
             xn = torch.empty_like(h)
             ops.rmsnorm(xn, h, self.layers[0].ln1, eps)
@@ -764,7 +710,6 @@ class LlamaModel:
         # 32K x 4: 232 vs 239; profiles/r6_qkv_attn_long_ab.log)
         one_part = -(-meta.bt_decode.shape[1] * self.block_size_hint // part) == 1
         L = len(self.layers)
-        lw0 = self.layers[0]
         for i, lw in enumerate(self.layers):
             kc, vc = kv_caches[i]
             win = cfg.window_of(i)
@@ -795,27 +740,14 @@ class LlamaModel:
             if pt is None or not fuse_qa:
                 ops.paged_decode(attn, qkv, kc, vc, meta.bt_decode, meta.ctx_decode, tmp_out, tmp_ml,
                                  nq, nkv, part, self.scale, win, attn16)
-            pt = self._partial(attn, lw.wo, attn16)
-            if lw.post_attn_norm is not None:  # Gemma sandwich norm
-                xn16 = self._x16(xn, lw.wgu) if pt is not None else None
-                xn8 = self._x8(xn, lw.wgu) if pt is not None else None
-                if not self.post_add_rmsnorm(xn, residual, pt, attn, lw.wo, lw.post_attn_norm, lw.ln2, xn16, xn8):
-                    xn16 = xn8 = None
-            elif pt is not None:
-                xn16 = self._x16(xn, lw.wgu) if lw.router is None else None
-                xn8 = self._x8(xn, lw.wgu) if lw.router is None else None
-                self.add_rmsnorm(xn, residual, pt[0], pt[1], lw.ln2, xn16, xn8)
-            else:
-                xn16 = xn8 = None
-                self.add_rmsnorm(xn, residual, self.linear_rowpar(attn, lw.wo), 1, lw.ln2)
+            xn16, xn8 = self._decode_rowpar_norm(xn, residual, attn, lw.wo, attn16, lw.post_attn_norm, lw.ln2, lw.wgu)
             nxt = self.layers[i + 1].ln1 if i + 1 < L else self.norm
             if lw.router is not None:  # MoE MLP: routed expert GEMMs, then residual + next norm
                 # TP = 1: the expert combine adds the residual and runs the next norm itself
                 # (moe_combine_add_rmsnorm, via _combine) and returns None
-                self._moe_norm = ((xn, residual, nxt) if self.tp.world_size == 1 and self.ops.name == "hip"
-                                  and residual.dtype == torch.bfloat16 else None)
-                y = self.moe(xn, lw)
-                self._moe_norm = None
+                tail = ((xn, residual, nxt) if self.tp.world_size == 1 and self.ops.name == "hip"
+                        and residual.dtype == torch.bfloat16 else None)
+                y = self.moe(xn, lw, tail=tail)
                 if y is not None:
                     self.add_rmsnorm(xn, residual, y, 1, nxt)
                 continue
@@ -823,8 +755,8 @@ class LlamaModel:
             gc = None if gelu else gemm.glu_choice(T, lw.wgu)
             pt = (None if gc is not None or (isinstance(lw.wgu, torch.Tensor) and not gelu)
                   else self._partial(xn, lw.wgu, xn16, xn8))
-            act16 = act8 = None
-            if gc is not None:     # SiLU-GLU in the gate|up GEMM's epilogue
+            act16 = None
+            if gc is not None:    # SiLU-GLU in the gate|up GEMM's epilogue
                 act = gemm.gemm_glu(xn, lw.wgu, gc)
             elif pt is not None:   # quantised gate|up, or GeGLU: the GLU over the plain-layout partials
                 act = torch.empty(T, self.inter, device=xn.device, dtype=xn.dtype)
@@ -838,45 +770,31 @@ class LlamaModel:
                 gu = self.linear(xn, lw.wgu)
                 act = torch.empty(T, self.inter, device=xn.device, dtype=xn.dtype)
                 self.act_and_mul(act, gu)
-            pt = self._partial(act, lw.wd, act16, act8)
-            if lw.post_ff_norm is not None:
-                xn16 = self._x16(xn, self.layers[i + 1].wqkv) if pt is not None and i + 1 < L else None
-                xn8 = self._x8(xn, self.layers[i + 1].wqkv) if pt is not None and i + 1 < L else None
-                if not self.post_add_rmsnorm(xn, residual, pt, act, lw.wd, lw.post_ff_norm, nxt, xn16, xn8):
-                    xn16 = xn8 = None
-            elif pt is not None:
-                xn16 = self._x16(xn, self.layers[i + 1].wqkv) if i + 1 < L else None
-                xn8 = self._x8(xn, self.layers[i + 1].wqkv) if i + 1 < L else None
-                self.add_rmsnorm(xn, residual, pt[0], pt[1], nxt, xn16, xn8)
-            else:
-                xn16 = xn8 = None
-                self.add_rmsnorm(xn, residual, self.linear_rowpar(act, lw.wd), 1, nxt)
+            consumer = self.layers[i + 1].wqkv if i + 1 < L else None
+            xn16, xn8 = self._decode_rowpar_norm(xn, residual, act, lw.wd, act16, lw.post_ff_norm, nxt, consumer)
         return xn
+
+    def _decode_rowpar_norm(self, xn, residual, x, w, x16, post_w, next_w, consumer):
+        """The fused decode layer's o_proj / down_proj tail: as ``_rowpar_norm``, over the
+        decode GEMM's split-K partials where the tuner picked it (``x16``: see ``_partial``),
+        else the unfused projection. Returns the (f16, e4m3) copies of xn the epilogue also
+        wrote for ``consumer``, the weight xn multiplies next (``_x16`` / ``_x8``; or None)."""
+        pt = self._partial(x, w, x16)
+        xn16 = self._x16(xn, consumer) if pt is not None else None
+        xn8 = self._x8(xn, consumer) if pt is not None else None
+        if post_w is not None:  # Gemma sandwich norm
+            if not self.post_add_rmsnorm(xn, residual, pt, x, w, post_w, next_w, xn16, xn8):
+                xn16 = xn8 = None
+        elif pt is not None:
+            self.add_rmsnorm(xn, residual, pt[0], pt[1], next_w, xn16, xn8)
+        else:
+            self.add_rmsnorm(xn, residual, self.linear_rowpar(x, w), 1, next_w)
+        return xn16, xn8
 
     def quant_weights(self) -> list:
         """Every GGUF-quantised projection (QuantWeight), lm_head included."""
-        from ..ops import quant as Q
         ws = [self.lm_head] + [getattr(lw, n) for lw in self.layers for n in ("wqkv", "wo", "wgu", "wd")]
         return [w for w in ws if isinstance(w, Q.QuantWeight)]
-
-    def _route(self, x: torch.Tensor, lw, k: int):
-        """(weights [T, k] fp32, expert ids [T, k] int32) of the top-k softmax over the
-        router logits x @ router^T. When the start-up timing picked the decode GEMM for the
-        router at this row count, its fp32 split-K partials go straight into the top-k
-        kernel, which sums and rounds them as splitk_reduce would (bit-identical, one
-        launch fewer per MoE layer)."""
-        op = torch.ops.hipserve
-        T, dev = x.shape[0], x.device
-        w = torch.empty(T, k, dtype=torch.float32, device=dev)
-        ids = torch.empty(T, k, dtype=torch.int32, device=dev)
-        fc = (gemm.fused_choice(T, lw.router)
-              if x.is_cuda and x.stride(1) == 1 and x.stride(0) % 8 == 0 else None)
-        if fc is not None:
-            ws, S = gemm.gemm_partial(x, lw.router, fc)
-            op.moe_topk_softmax(w, ids, ws, k, self.cfg.norm_topk_prob, S)
-        else:
-            op.moe_topk_softmax(w, ids, gemm.linear(x, lw.router), k, self.cfg.norm_topk_prob)
-        return w, ids
 
     def _partial(self, x: torch.Tensor, w, x16: torch.Tensor | None = None, x8=None):
         """(fp32 split-K partials [S, M, N], S) of ``x @ w.T`` for a fused decode
@@ -886,7 +804,6 @@ class LlamaModel:
         if isinstance(w, (torch.Tensor, gemm.PackedLinear)):
             fc = gemm.fused_choice(x.shape[0], w)
             return gemm.gemm_partial(x, w, fc) if fc is not None else None
-        from ..ops import quant as Q
         M = x.shape[0]
         # FP8 W8A8 above 64 rows: TP = 1 (the cross-rank epilogues are sized for <= 64 rows)
         if getattr(w, "v2", False) and x.is_cuda and (M <= Q.MAX_FUSED_M or (
@@ -904,7 +821,6 @@ class LlamaModel:
         (splitk_add_rmsnorm / splitk_glu / the decode attention) writes when the consumer is
         a quantised decode GEMM at 33-64 rows (gguf_mfma.hip stages it as is instead of
         converting x in every workgroup); None otherwise."""
-        from ..ops import quant as Q
         if (not self.X16 or self.tp.world_size != 1 or not like.is_cuda or not 32 < like.shape[0] <= 64
                 or not getattr(consumer, "v2", False) or not hasattr(torch.ops.hipserve, "splitk_glu")
                 or Q.f8_decode_ok(consumer)):  # the W8A8 decode GEMM quantises x itself
@@ -927,7 +843,6 @@ class LlamaModel:
         ``like`` that its producer (splitk_add_rmsnorm / splitk_post_add_rmsnorm) writes
         when the consumer runs the W8A8 FP8 decode GEMM (bit-identical to quantising
         ``like`` afterwards; one act_quant_fp8 launch fewer); None otherwise."""
-        from ..ops import quant as Q
         if (self.tp.world_size != 1 or not like.is_cuda or like.shape[0] > Q.F8_DECODE_MAX_M
                 or not Q.f8_decode_ok(consumer)):
             return None
@@ -958,353 +873,6 @@ class LlamaModel:
         to = to.view(-1)[: Td * nq * mp * D].view(Td, nq, mp, D)
         tm = tm.view(-1)[: Td * nq * mp * 2].view(Td, nq, mp, 2)
         return part, to, tm
-
-    # (out, residual, norm weight) of the decode layer's MoE tail: set around ``moe`` by
-    # forward_decode_fused at TP = 1 so the combine also does residual add + next RMSNorm
-    _moe_norm: tuple | None = None
-
-    def _combine(self, out: torch.Tensor, y: torch.Tensor, S: int, w, pair_slot, k: int):
-        """Weighted combine of a token's k expert rows (bf16 ``y`` [slots, H] when S == 0,
-        fp32 split-K partials [S, slots, H] else) into ``out``. Under ``_moe_norm`` the
-        one-kernel combine + residual add + next-layer RMSNorm instead (bit-identical to
-        combine then fused_add_rmsnorm): writes the norm output and the residual in place,
-        returns None."""
-        op = torch.ops.hipserve
-        if self._moe_norm is not None:
-            xn, residual, nw = self._moe_norm
-            self._moe_norm = None
-            op.moe_combine_add_rmsnorm(xn, residual, y, S, w, pair_slot, k, nw, self.cfg.rms_norm_eps)
-            return None
-        if S > 0:
-            op.moe_combine_partial(out, y, w, pair_slot, k)
-        else:
-            op.moe_combine(out, y, w, pair_slot, k)
-        return out
-
-    def moe(self, x: torch.Tensor, lw: LayerWeights) -> torch.Tensor | None:
-        """Sparse MoE: softmax over the E router logits, top-k experts, weights
-        renormalised over the k (Mixtral; Qwen3-MoE when ``norm_topk_prob``).
-
-        On the GPU every batch runs one of the two graph-capturable kernel paths:
-        ``moe_hip`` (the weight-streaming expert decode GEMM; decode batches, and
-        prefill batches below the start-up-timed crossover ``moe_packed_from_tokens``)
-        or ``moe_grouped`` (the packed-layout one-launch grouped GEMM). The per-expert
-        loop at the end is the CPU reference path only."""
-        cfg = self.cfg
-        k = cfg.num_experts_per_tok
-        T = x.shape[0]
-        P = T * k
-        hip = self.ops.name == "hip"
-        if lw.w13 is not None and not isinstance(lw.w13, torch.Tensor):  # quantised experts (ops/quant.py QuantMoE)
-            if P <= MOE_KERNEL_MAX_PAIRS:
-                return self.moe_quant(x, lw)
-            from ..ops import quant as Q
-
-            if (hip and self._moe_packed_shape_ok() and lw.w13.dense is None
-                    and self.moe_prefill_choice(T) == "packed"):
-                # experts dequantised straight into the packed layout, then the one-launch grouped GEMMs
-                lw = LayerWeights(ln1=None, wqkv=None, wo=None, ln2=None, router=lw.router,
-                                  moe_packed=(Q.moe_packed_scratch(lw.w13, 0, True),
-                                              Q.moe_packed_scratch(lw.w2, 1, False)))
-                return self.moe_grouped(x, lw)
-            lw = LayerWeights(ln1=None, wqkv=None, wo=None, ln2=None, router=lw.router,
-                              w13=Q.moe_dense(lw.w13, 0), w2=Q.moe_dense(lw.w2, 1))
-        if hip:
-            kernel_ok = (cfg.num_experts <= 128 and cfg.hidden_size % 256 == 0 and self.inter % 256 == 0
-                         and (lw.w13 is not None or lw.moe_packed is not None))
-            grouped_ok = self.moe_packed_prefill(lw)
-            if kernel_ok and (P <= MOE_KERNEL_MAX_PAIRS or not grouped_ok
-                              or (P <= MOE_KERNEL_MAX_ROWS_PER_EXPERT * cfg.num_experts
-                                  and self.moe_prefill_choice(T) == "hip")):
-                return self.moe_hip(x, lw)
-            if grouped_ok:
-                return self.moe_grouped(x, lw)
-            raise NotImplementedError(f"MoE shape (E={cfg.num_experts}, H={cfg.hidden_size}, I={self.inter}) "
-                                      "has no gfx950 expert kernel")
-        logits = F.linear(x, lw.router).float()
-        w, idx = torch.topk(torch.softmax(logits, dim=-1), k, dim=-1)
-        if cfg.norm_topk_prob:
-            w = w / w.sum(-1, keepdim=True)
-        out = torch.zeros(T, cfg.hidden_size, device=x.device, dtype=torch.float32)
-        flat_idx = idx.reshape(-1)
-        flat_tok = torch.arange(T, device=x.device).repeat_interleave(k)
-        flat_w = w.reshape(-1)
-        order = torch.argsort(flat_idx)
-        counts = torch.bincount(flat_idx, minlength=cfg.num_experts).tolist()
-        start = 0
-        for e, n in enumerate(counts):
-            if n == 0:
-                continue
-            sel = order[start:start + n]
-            start += n
-            toks = flat_tok[sel]
-            gu = F.linear(x[toks], lw.w13[e])
-            act = torch.empty(n, self.inter, device=x.device, dtype=x.dtype)
-            self.ops.silu_and_mul(act, gu)
-            y = F.linear(act, lw.w2[e]).float() * flat_w[sel].unsqueeze(-1)
-            out.index_add_(0, toks, y)
-        return out.to(x.dtype)
-
-    def _moe_decode_ok(self, lw: LayerWeights) -> bool:
-        """Shapes the expert decode GEMM (decode_gemm.hip kMoe) takes: K = H for w13
-        (one K slice of 256 * {1,2,4,7,8,16}) and K = I/TP for w2 (split over K)."""
-        H, I = self.cfg.hidden_size, self.inter
-        return ((H // 256) in DG_MOE_STEPS and H % 256 == 0 and I % 256 == 0 and (2 * I) % 128 == 0
-                and self._moe_w2_splits(I, 1, 1) > 0)
-
-    @staticmethod
-    def _moe_w2_splits(K: int, ntiles: int, active: int) -> int:
-        """Split-K factor of the w2 expert GEMM: the fewest K slices (of 256 * one of
-        DG_MOE_STEPS) that give >= 1024 workgroups over the active expert tiles."""
-        ks = K // 256
-        opts = sorted(ks // st for st in DG_MOE_STEPS if ks % st == 0)
-        if not opts:
-            return 0
-        for S in opts:
-            if ntiles * S * active >= 1024:
-                return S
-        return opts[-1]
-
-    def moe_grouped(self, x: torch.Tensor, lw: LayerWeights) -> torch.Tensor:
-        """Prefill-sized MoE: routing (top-k kernel), expert-sorted slots padded to the
-        GEMM's row tile (moe_align), then the two expert GEMMs as ONE launch each on the
-        packed expert layout (prefill_gemm_packed.hip kGroup: expert ids read on the
-        device, no host round trip, graph-capturable; the token rows gathered through the
-        slot table inside the first GEMM's X loads, SiLU-GLU in its epilogue), and the
-        weighted combine (moe_combine). Row-major experts without a packed copy (tests)
-        are packed into a scratch first."""
-        op = torch.ops.hipserve
-        cfg = self.cfg
-        E, k, H = cfg.num_experts, cfg.num_experts_per_tok, cfg.hidden_size
-        T, dev = x.shape[0], x.device
-        if lw.moe_packed is None:
-            p13 = torch.empty(E, 2 * self.inter * H, dtype=lw.w13.dtype, device=dev)
-            p2 = torch.empty(E, -(-H // 128) * 128 * self.inter, dtype=lw.w2.dtype, device=dev)
-            op.pack_decode_weight(p13, lw.w13.contiguous(), True)
-            op.pack_decode_weight(p2, lw.w2.contiguous(), False)
-            lw = LayerWeights(ln1=None, wqkv=None, wo=None, ln2=None, router=lw.router, moe_packed=(p13, p2))
-        P = T * k
-        tile = 128 * gemm.PW_WM
-        cap = -(-(P + E * (tile - 1)) // tile) * tile
-        w, ids = self._route(x, lw, k)
-        slots = torch.empty(cap, dtype=torch.int32, device=dev)
-        tile_expert = torch.empty(cap // tile, dtype=torch.int32, device=dev)
-        ntiles = torch.empty(1, dtype=torch.int32, device=dev)
-        pair_slot = torch.empty(P, dtype=torch.int32, device=dev)
-        ends = torch.empty(E, dtype=torch.int32, device=dev)
-        op.moe_align(ids, E, tile, slots, tile_expert, ntiles, pair_slot, ends)
-        p13, p2 = lw.moe_packed
-        act = torch.empty(cap, self.inter, dtype=x.dtype, device=dev)
-        # the first GEMM reads its token rows through the slot table (moe_gather fused)
-        op.prefill_gemm_packed_grouped(act, x, p13, 2 * self.inter, 2, tile_expert, ntiles, gemm.PW_WM, gemm.PW_RW,
-                                       slots, k)
-        y = torch.empty(cap, H, dtype=x.dtype, device=dev)
-        op.prefill_gemm_packed_grouped(y, act, p2, H, 0, tile_expert, ntiles, gemm.PW_WM, gemm.PW_RW)
-        return self._combine(torch.empty(T, H, dtype=x.dtype, device=dev), y, 0, w, pair_slot, k)
-
-    # prefill-sized MoE batches: the packed one-launch grouped GEMM (``moe_grouped``) or the
-    # weight-streaming expert kernel (``moe_hip``). ``auto``: by the start-up timing of the
-    # layer's expert shape at several token counts (``tune_moe_prefill``): the grouped GEMM
-    # from ``moe_packed_from_tokens`` tokens up, the streaming kernel below (its 128-row
-    # tiles are mostly padding when 128 experts share a few hundred tokens). ``1`` / ``0``
-    # force the grouped GEMM / the streaming kernel. hipBLASLt's grouped GEMM
-    # (torch._grouped_mm) lost to the packed kernel on every shipped MoE config (Mixtral
-    # 4.82 vs 5.10 ms, Qwen3-30B-A3B 1.52 vs 5.17 ms per layer at 16K tokens,
-    # profiles/r5_bench_mixtral_gather_fused.json, r5_bench_q3int8_align_multiblock.json)
-    # and read its group offsets on the host: removed
-    MOE_PACKED_PREFILL = os.environ.get("HIPSERVE_MOE_PACKED_PREFILL", "auto")
-    moe_prefill_path: str | None = None  # "hip" | "packed" at the timed budget, set by tune_moe_prefill
-    moe_packed_from_tokens: int = 0     # "packed": the grouped GEMM from this many tokens up
-
-    @property
-    def moe_prefill_packed(self) -> bool:
-        return self.moe_prefill_path == "packed"
-
-    def moe_prefill_choice(self, T: int) -> str:
-        """'packed' (grouped GEMM) or 'hip' (streaming expert kernel) for a T-token batch."""
-        mode = self.MOE_PACKED_PREFILL
-        if mode in ("0", "1"):
-            return "packed" if mode == "1" else "hip"
-        if self.moe_prefill_path == "packed" and T >= self.moe_packed_from_tokens:
-            return "packed"
-        if self.moe_prefill_path is None:  # untimed (tests, CPU): the grouped GEMM above the kernel row limit
-            E, k = self.cfg.num_experts, self.cfg.num_experts_per_tok
-            return "packed" if T * k > MOE_KERNEL_MAX_ROWS_PER_EXPERT * E else "hip"
-        return "hip"
-
-    def _moe_packed_shape_ok(self) -> bool:
-        return (self.cfg.hidden_act == "silu" and self.cfg.hidden_size % 256 == 0 and self.inter % 256 == 0
-                and (2 * self.inter) % 128 == 0 and hasattr(torch.ops.hipserve, "prefill_gemm_packed_grouped"))
-
-    def moe_packed_prefill(self, lw: LayerWeights, for_drop: bool = False) -> bool:
-        """The packed-layout grouped GEMM can run this layer's prefill: SiLU-GLU experts,
-        K of both GEMMs % 256, a packed copy (or row-major experts to pack from)."""
-        if not self._moe_packed_shape_ok() or (lw.moe_packed is None and lw.w13 is None):
-            return False
-        if for_drop:
-            return self.MOE_PACKED_PREFILL != "0" and lw.moe_packed is not None
-        return True
-
-    @torch.inference_mode()
-    def tune_moe_prefill(self, T: int) -> dict | None:
-        """Start-up timing of one MoE layer's prefill on random bf16 experts of the layer's
-        shape through the model's own paths, the weight-streaming expert kernel
-        (``moe_hip``, where its row limit allows) vs the packed one-launch grouped GEMM
-        (``moe_grouped``), at ``T`` tokens and at halvings of it down to the decode
-        kernels' pair limit. Sets ``moe_prefill_path`` (the winner at T) and
-        ``moe_packed_from_tokens`` (the smallest timed count from which the grouped GEMM
-        wins at every larger count). Cached per device and kernel build."""
-        from ..ops import tune_cache as TC
-
-        cfg = self.cfg
-        lw = next((lw for lw in self.layers if lw.router is not None), None)
-        if (lw is None or not self._moe_packed_shape_ok() or self.MOE_PACKED_PREFILL != "auto"
-                or getattr(self.ops, "name", "") != "hip" or self.device.type != "cuda" or cfg.num_experts > 128):
-            return None
-        E, k, H, I = cfg.num_experts, cfg.num_experts_per_tok, cfg.hidden_size, self.inter
-        quant = lw.w13 is not None and not isinstance(lw.w13, torch.Tensor)
-        if not quant and lw.moe_packed is None and lw.w13 is None:
-            return None
-        key = [E, k, H, I, T, quant, "v2"]
-        hit = TC.get(self.device, "moe_prefill", key)
-        if hit is not None:
-            self.moe_prefill_path, self.moe_packed_from_tokens = hit["path"], hit["packed_from_tokens"]
-            return dict(hit, cached=True)
-        op, dev = torch.ops.hipserve, self.device
-        g = torch.Generator(device=dev).manual_seed(E * H + I)
-        w13 = (torch.randn(E, 2 * I, H, device=dev, generator=g) * 0.02).to(torch.bfloat16)
-        w2 = (torch.randn(E, H, I, device=dev, generator=g) * 0.02).to(torch.bfloat16)
-        p13 = torch.empty(E, 2 * I * H, dtype=torch.bfloat16, device=dev)
-        p2 = torch.empty(E, -(-H // 128) * 128 * I, dtype=torch.bfloat16, device=dev)
-        op.pack_decode_weight(p13, w13, True)
-        op.pack_decode_weight(p2, w2, False)
-        router = (torch.randn(E, H, device=dev, generator=g) * 0.3).to(torch.bfloat16)
-        syn = LayerWeights(ln1=None, wqkv=None, wo=None, ln2=None, router=router, w13=w13, w2=w2,
-                           moe_packed=(p13, p2))
-        counts = []
-        t = T
-        while t * k > MOE_KERNEL_MAX_PAIRS and len(counts) < 5:
-            counts.append(t)
-            t //= 2
-        rows = []
-        for t in counts:
-            x = torch.randn(t, H, device=dev, generator=g).to(torch.bfloat16)
-            # quantised experts dequantise once per step on either path: only the GEMMs are timed
-            row = {"tokens": t, "packed_ms": round(pgemm._time(lambda i: self.moe_grouped(x, syn), reps=2), 3)}
-            if not quant and t * k <= MOE_KERNEL_MAX_ROWS_PER_EXPERT * E and self._moe_decode_ok(syn):
-                row["hip_ms"] = round(pgemm._time(lambda i: self.moe_hip(x, syn), reps=2), 3)
-            rows.append(row)
-        del w13, w2, p13, p2, syn
-        torch.cuda.empty_cache()
-        wins = [r.get("hip_ms") is None or r["packed_ms"] < r["hip_ms"] for r in rows]
-        best = "packed" if not rows or wins[0] else "hip"
-        frm = T
-        for r, w_ in zip(rows, wins):  # counts descend: the grouped GEMM's run of wins from the top
-            if not w_:
-                break
-            frm = r["tokens"]
-        if best == "packed" and len(rows) and all(wins):
-            frm = 0  # wins down to the pair limit: every prefill-sized batch
-        self.moe_prefill_path, self.moe_packed_from_tokens = best, frm
-        r = {"E": E, "H": H, "I": I, "tokens": T, "quant": quant, "path": best, "packed_from_tokens": frm,
-             "timing": rows}
-        TC.put(self.device, "moe_prefill", key, r)
-        TC.flush()
-        log.info("MoE prefill expert GEMMs: %s", r)
-        return r
-
-    def moe_hip(self, x: torch.Tensor, lw: LayerWeights) -> torch.Tensor:
-        """Graph-capturable MoE on the gfx950 kernels (decode-sized batches): top-k
-        routing, expert-sorted 16/32/64-row tiles, two gathered MFMA GEMMs with the
-        SiLU*up in between, weighted combine. No host synchronisation.
-
-        The expert GEMMs are the decode GEMM in its MoE mode (weight-streaming:
-        128 weight rows x one expert tile per workgroup, x tile staged in LDS):
-        with packed weights (``pack_moe_weights``) the SiLU-GLU runs in the w13
-        epilogue, and w2 writes split-K fp32 partials that the combine sums."""
-        op = torch.ops.hipserve
-        cfg = self.cfg
-        E, k, H = cfg.num_experts, cfg.num_experts_per_tok, cfg.hidden_size
-        T, dev = x.shape[0], x.device
-        P = T * k
-        tile = 16 if P <= 8 * E else (32 if P <= 32 * E else 64)
-        cap = -(-(P + E * (tile - 1)) // tile) * tile
-        w, ids = self._route(x, lw, k)
-        slots = torch.empty(cap, dtype=torch.int32, device=dev)
-        tile_expert = torch.empty(cap // tile, dtype=torch.int32, device=dev)
-        ntiles = torch.empty(1, dtype=torch.int32, device=dev)
-        pair_slot = torch.empty(P, dtype=torch.int32, device=dev)
-        op.moe_align(ids, E, tile, slots, tile_expert, ntiles, pair_slot)
-        out = torch.empty(T, H, dtype=x.dtype, device=dev)
-        if self._moe_decode_ok(lw):
-            packed = lw.moe_packed is not None
-            act = torch.empty(cap, self.inter, dtype=x.dtype, device=dev)
-            if packed:
-                op.moe_decode_gemm(act, x, lw.moe_packed[0], slots, tile_expert, tile, k, 2 * self.inter, 1,
-                                   True, True)
-            else:
-                gu = torch.empty(cap, 2 * self.inter, dtype=x.dtype, device=dev)
-                op.moe_decode_gemm(gu, x, lw.w13, slots, tile_expert, tile, k, 2 * self.inter, 1, False, False)
-                self.ops.silu_and_mul(act, gu)
-            active = min(E, cap // tile, P)
-            S = self._moe_w2_splits(self.inter, -(-H // 128), active)
-            w2 = lw.moe_packed[1] if packed else lw.w2
-            if S == 1:  # one K slice: bf16 expert outputs, no fp32 partial slab
-                y = torch.empty(cap, H, dtype=x.dtype, device=dev)
-                op.moe_decode_gemm(y, act, w2, slots, tile_expert, tile, 0, H, 1, packed, False)
-                return self._combine(out, y, 0, w, pair_slot, k)
-            ws = torch.empty(S, cap, H, dtype=torch.float32, device=dev)
-            op.moe_decode_gemm(ws, act, w2, slots, tile_expert, tile, 0, H, S, packed, False)
-            return self._combine(out, ws, S, w, pair_slot, k)
-        gu = torch.empty(cap, 2 * self.inter, dtype=x.dtype, device=dev)
-        op.moe_gemm(gu, x, lw.w13, slots, tile_expert, tile, k)
-        act = torch.empty(cap, self.inter, dtype=x.dtype, device=dev)
-        self.ops.silu_and_mul(act, gu)
-        y = torch.empty(cap, H, dtype=x.dtype, device=dev)
-        op.moe_gemm(y, act, lw.w2, slots, tile_expert, tile, 0)
-        return self._combine(out, y, 0, w, pair_slot, k)
-
-    def moe_quant(self, x: torch.Tensor, lw: LayerWeights) -> torch.Tensor:
-        """Decode-sized MoE on quantised experts (INT8 / FP8, ``QuantMoE``): routing and
-        expert-sorted tiles as ``moe_hip``, then the dequant-MFMA expert GEMM in its
-        MoE mode (gathered token rows, one expert's weight stream per workgroup) for
-        w13, SiLU-GLU, and w2 (split over K into fp32 partials summed by the
-        weighted combine). No host synchronisation (graph-capturable)."""
-        op = torch.ops.hipserve
-        cfg = self.cfg
-        E, k, H = cfg.num_experts, cfg.num_experts_per_tok, cfg.hidden_size
-        T, dev = x.shape[0], x.device
-        P = T * k
-        tile = 16 if P <= 8 * E else (32 if P <= 32 * E else 64)
-        cap = -(-(P + E * (tile - 1)) // tile) * tile
-        w, ids = self._route(x, lw, k)
-        slots = torch.empty(cap, dtype=torch.int32, device=dev)
-        tile_expert = torch.empty(cap // tile, dtype=torch.int32, device=dev)
-        ntiles = torch.empty(1, dtype=torch.int32, device=dev)
-        pair_slot = torch.empty(P, dtype=torch.int32, device=dev)
-        op.moe_align(ids, E, tile, slots, tile_expert, ntiles, pair_slot)
-        w13, w2 = lw.w13, lw.w2
-        f32 = torch.empty(0, dtype=torch.float32, device=dev)
-        act = torch.empty(cap, w13.N // 2, dtype=x.dtype, device=dev)
-        if tile <= 32 and (w13.N // 2) % 16 == 0:  # GLU in the w13 epilogue (bit-identical)
-            glu = 2 if cfg.hidden_act == "gelu_tanh" else 1
-            op.qmoe_gemm(act, f32, x, w13.q, w13.rs, w13.kqt, w13.N, w13.K, slots, tile_expert, tile, k, 1,
-                         w13.kmajor, glu)
-        else:
-            gu = torch.empty(cap, w13.N, dtype=x.dtype, device=dev)
-            op.qmoe_gemm(gu, f32, x, w13.q, w13.rs, w13.kqt, w13.N, w13.K, slots, tile_expert, tile, k, 1,
-                         w13.kmajor)
-            self.act_and_mul(act, gu)
-        out = torch.empty(T, H, dtype=x.dtype, device=dev)
-        active = min(E, cap // tile, P)
-        S = self._moe_w2_splits(w2.K, -(-H // 128), active)
-        if S <= 1:
-            y = torch.empty(cap, H, dtype=x.dtype, device=dev)
-            op.qmoe_gemm(y, f32, act, w2.q, w2.rs, w2.kqt, w2.N, w2.K, slots, tile_expert, tile, 0, 1, w2.kmajor)
-            return self._combine(out, y, 0, w, pair_slot, k)
-        ws = torch.empty(S, cap, H, dtype=torch.float32, device=dev)
-        S = op.qmoe_gemm(out, ws, act, w2.q, w2.rs, w2.kqt, w2.N, w2.K, slots, tile_expert, tile, 0, S, w2.kmajor)
-        return self._combine(out, ws[:S], S, w, pair_slot, k)
 
     def compute_logits(self, hidden: torch.Tensor) -> torch.Tensor:
         logits = self.linear(hidden, self.lm_head)
