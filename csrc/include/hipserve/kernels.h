@@ -253,11 +253,13 @@ void launch_pack_decode_weight(void* out, const void* w, int N, int K, bool glu,
 
 namespace hipserve {
 // moe.hip — tile in {16, 32, 64}
+// moe_align: E experts starting at expert_lo are aligned (tile_expert / group_end hold the
+// local id ids[p] - expert_lo); a pair of any other expert gets pair_slot = -1 and no slot
 void launch_moe_topk_softmax(const void* logits, bool logits_f32, float* w, int* ids, int T, int E, int k,
                              bool renorm, hipStream_t s, int splits = 0);
 void launch_moe_align(const int* ids, int npairs, int E, int tile, int* slots, int slots_cap, int* tile_expert,
                       int tiles_cap, int* num_tiles, int* pair_slot, int* group_end, hipStream_t s,
-                      int* hist = nullptr);
+                      int* hist = nullptr, int expert_lo = 0);
 // blocks of the multi-workgroup moe_align for npairs (1: the single-workgroup kernel);
 // it needs hist = int32 [blocks * 128] scratch
 int moe_align_blocks(int npairs);

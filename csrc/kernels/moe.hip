@@ -5,7 +5,10 @@
 //   moe_topk_softmax  router logits -> top-k experts + renormalised weights
 //                     (one wave per token, experts on lanes, wave64 reductions)
 //   moe_align         token/expert pairs sorted by expert into 16-row tiles,
-//                     padding slots = -1 (one 1024-thread workgroup, LDS counts)
+//                     padding slots = -1 (one 1024-thread workgroup, LDS counts);
+//                     with an expert range [lo, lo + E) (expert-parallel ranks) only
+//                     the pairs of those experts take a slot, the others get
+//                     pair_slot = -1 and the combine kernels skip them
 //   moe_gemm          per tile: out[slot] = x[row(slot)] . W_e^T on MFMA, rows
 //                     gathered through the slot list (token rows for w13, slot rows
 //                     for w2); each expert's weights stream once per 16-row tile
@@ -92,12 +95,17 @@ __global__ __launch_bounds__(1024) void moe_align_kernel(const int* __restrict__
                                                          int* __restrict__ slots, int slots_cap,
                                                          int* __restrict__ tile_expert, int tiles_cap,
                                                          int* __restrict__ num_tiles, int* __restrict__ pair_slot,
-                                                         int* __restrict__ group_end) {
+                                                         int* __restrict__ group_end, int lo) {
+  // experts are counted and placed by their local id ids[p] - lo; a pair whose expert is
+  // outside [lo, lo + E) (one unsigned compare) is another rank's: no slot, pair_slot = -1
   __shared__ int cnt[128], off[129], cur[128];
   const int tid = threadIdx.x, lane = tid & 63;
   if (tid < 128) { cnt[tid] = 0; cur[tid] = 0; }
   __syncthreads();
-  for (int p = tid; p < npairs; p += 1024) atomicAdd(&cnt[ids[p]], 1);
+  for (int p = tid; p < npairs; p += 1024) {
+    const unsigned e = (unsigned)(ids[p] - lo);
+    if (e < (unsigned)E) atomicAdd(&cnt[e], 1);
+  }
   __syncthreads();
   if (tid < 64) {  // exclusive scan of the tile-padded counts, 2 experts per lane (E <= 128)
     const int e0 = 2 * lane, e1 = 2 * lane + 1;
@@ -130,7 +138,11 @@ __global__ __launch_bounds__(1024) void moe_align_kernel(const int* __restrict__
   for (int t = total / tile + tid; t < tiles_cap; t += 1024) tile_expert[t] = -1;
   __syncthreads();
   for (int p = tid; p < npairs; p += 1024) {
-    const int e = ids[p];
+    const unsigned e = (unsigned)(ids[p] - lo);
+    if (e >= (unsigned)E) {
+      pair_slot[p] = -1;
+      continue;
+    }
     const int pos = off[e] + atomicAdd(&cur[e], 1);
     slots[pos] = p;
     pair_slot[p] = pos;
@@ -144,14 +156,17 @@ __global__ __launch_bounds__(1024) void moe_align_kernel(const int* __restrict__
 // the tile count and the padding slots (disjoint from every real slot, so no ordering
 // between blocks is needed).
 constexpr int kAlignChunk = 4096;
-__global__ __launch_bounds__(1024) void moe_count_kernel(const int* __restrict__ ids, int npairs,
+__global__ __launch_bounds__(1024) void moe_count_kernel(const int* __restrict__ ids, int npairs, int E, int lo,
                                                          int* __restrict__ hist) {
   __shared__ int cnt[128];
   const int tid = threadIdx.x, b = blockIdx.x;
   if (tid < 128) cnt[tid] = 0;
   __syncthreads();
   const int end = min(npairs, (b + 1) * kAlignChunk);
-  for (int p = b * kAlignChunk + tid; p < end; p += 1024) atomicAdd(&cnt[ids[p]], 1);
+  for (int p = b * kAlignChunk + tid; p < end; p += 1024) {
+    const unsigned e = (unsigned)(ids[p] - lo);  // local expert id; other ranks' pairs are not counted
+    if (e < (unsigned)E) atomicAdd(&cnt[e], 1);
+  }
   __syncthreads();
   if (tid < 128) hist[b * 128 + tid] = cnt[tid];
 }
@@ -161,7 +176,7 @@ __global__ __launch_bounds__(1024) void moe_place_kernel(const int* __restrict__
                                                          int* __restrict__ slots, int slots_cap,
                                                          int* __restrict__ tile_expert, int tiles_cap,
                                                          int* __restrict__ num_tiles, int* __restrict__ pair_slot,
-                                                         int* __restrict__ group_end) {
+                                                         int* __restrict__ group_end, int lo) {
   __shared__ int cnt[128], pre[128], off[129], cur[128];
   const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
   if (tid < 128) {  // expert totals and this block's prefix over the blocks before it
@@ -211,7 +226,11 @@ __global__ __launch_bounds__(1024) void moe_place_kernel(const int* __restrict__
   }
   const int end = min(npairs, (b + 1) * kAlignChunk);
   for (int p = b * kAlignChunk + tid; p < end; p += 1024) {
-    const int e = ids[p];
+    const unsigned e = (unsigned)(ids[p] - lo);
+    if (e >= (unsigned)E) {
+      pair_slot[p] = -1;
+      continue;
+    }
     const int pos = off[e] + pre[e] + atomicAdd(&cur[e], 1);
     slots[pos] = p;
     pair_slot[p] = pos;
@@ -290,8 +309,10 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(unsigned short* __rest
   for (int c = threadIdx.x; c < H / 8; c += 256) {
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < k; ++j) {
+      const int ps = pair_slot[t * k + j];
+      if (ps < 0) continue;  // another rank's expert (moe_align with an expert range): block-uniform
       const float wt = w[(long)t * k + j];
-      const u16x8 v = *reinterpret_cast<const u16x8*>(y + (long)pair_slot[t * k + j] * H + 8 * c);
+      const u16x8 v = *reinterpret_cast<const u16x8*>(y + (long)ps * H + 8 * c);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[e] += wt * bf16_to_f32(v[e]);
     }
@@ -312,8 +333,10 @@ __global__ __launch_bounds__(256) void moe_combine_partial_kernel(unsigned short
   for (int c = threadIdx.x; c < H / 8; c += 256) {
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < k; ++j) {
+      const int ps = pair_slot[t * k + j];
+      if (ps < 0) continue;  // another rank's expert: block-uniform skip
       const float wt = w[(long)t * k + j];
-      const float* p = ws + (long)pair_slot[t * k + j] * H + 8 * c;
+      const float* p = ws + (long)ps * H + 8 * c;
       f32x4 lo, hi;
       sum_slices8(lo, hi, p, slab, S);
 #pragma unroll
@@ -448,16 +471,17 @@ void launch_moe_topk_softmax(const void* logits, bool logits_f32, float* w, int*
 }
 
 void launch_moe_align(const int* ids, int npairs, int E, int tile, int* slots, int slots_cap, int* tile_expert,
-                      int tiles_cap, int* num_tiles, int* pair_slot, int* group_end, hipStream_t s, int* hist) {
+                      int tiles_cap, int* num_tiles, int* pair_slot, int* group_end, hipStream_t s, int* hist,
+                      int expert_lo) {
   const int nb = moe_align_blocks(npairs);
   if (nb > 1 && hist != nullptr) {
-    moe_count_kernel<<<nb, 1024, 0, s>>>(ids, npairs, hist);
+    moe_count_kernel<<<nb, 1024, 0, s>>>(ids, npairs, E, expert_lo, hist);
     moe_place_kernel<<<nb, 1024, 0, s>>>(ids, npairs, E, tile, hist, nb, slots, slots_cap, tile_expert, tiles_cap,
-                                         num_tiles, pair_slot, group_end);
+                                         num_tiles, pair_slot, group_end, expert_lo);
     return;
   }
   moe_align_kernel<<<1, 1024, 0, s>>>(ids, npairs, E, tile, slots, slots_cap, tile_expert, tiles_cap, num_tiles,
-                                      pair_slot, group_end);
+                                      pair_slot, group_end, expert_lo);
 }
 
 // Prefill MoE input: xs[slot] = x[slots[slot] / k] (the token of the pair in that

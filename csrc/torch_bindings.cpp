@@ -1106,11 +1106,12 @@ void pack_decode_weight(at::Tensor& out, const at::Tensor& w, bool glu) {
 }
 
 void moe_align(const at::Tensor& ids, int64_t E, int64_t tile, at::Tensor& slots, at::Tensor& tile_expert,
-               at::Tensor& num_tiles, at::Tensor& pair_slot, const c10::optional<at::Tensor>& group_end) {
+               at::Tensor& num_tiles, at::Tensor& pair_slot, const c10::optional<at::Tensor>& group_end,
+               int64_t expert_lo) {
   CHECK_DEV(ids);
   TORCH_CHECK(ids.scalar_type() == at::kInt && slots.scalar_type() == at::kInt &&
               tile_expert.scalar_type() == at::kInt && pair_slot.scalar_type() == at::kInt);
-  TORCH_CHECK(E <= 128 && (tile == 16 || tile == 32 || tile == 64 || tile == 128 || tile == 256));
+  TORCH_CHECK(E >= 1 && E <= 128 && expert_lo >= 0 && expert_lo <= (1 << 20) && (tile == 16 || tile == 32 || tile == 64 || tile == 128 || tile == 256));
   const int npairs = ids.numel();
   TORCH_CHECK(slots.numel() >= npairs + E * (tile - 1) && slots.numel() % tile == 0,
               "slots capacity must cover padding and be a multiple of the tile");
@@ -1126,7 +1127,8 @@ void moe_align(const at::Tensor& ids, int64_t E, int64_t tile, at::Tensor& slots
   if (nb > 1) hist = at::empty({(long)nb * 128}, ids.options().dtype(at::kInt));
   hipserve::launch_moe_align(ids.data_ptr<int>(), npairs, E, tile, slots.data_ptr<int>(), slots.numel(),
                              tile_expert.data_ptr<int>(), tile_expert.numel(), num_tiles.data_ptr<int>(),
-                             pair_slot.data_ptr<int>(), ge, cur_stream(), nb > 1 ? hist.data_ptr<int>() : nullptr);
+                             pair_slot.data_ptr<int>(), ge, cur_stream(), nb > 1 ? hist.data_ptr<int>() : nullptr,
+                             (int)expert_lo);
 }
 
 void moe_gather(at::Tensor& out, const at::Tensor& x, const at::Tensor& slots, int64_t k) {
@@ -1294,7 +1296,7 @@ void vision_attention(at::Tensor& out, at::Tensor& qkv, const at::Tensor& cos_si
 TORCH_LIBRARY(hipserve, m) {
   m.def("moe_topk_softmax(Tensor(a!) w, Tensor(b!) ids, Tensor logits, int k, bool renorm=True, int splits=0) -> ()");
   m.def("moe_combine_add_rmsnorm(Tensor(a!) out, Tensor(b!) residual, Tensor y, int splits, Tensor w, Tensor pair_slot, int k, Tensor norm_w, float eps) -> ()");
-  m.def("moe_align(Tensor ids, int E, int tile, Tensor(a!) slots, Tensor(b!) tile_expert, Tensor(c!) num_tiles, Tensor(d!) pair_slot, Tensor(e!)? group_end=None) -> ()");
+  m.def("moe_align(Tensor ids, int E, int tile, Tensor(a!) slots, Tensor(b!) tile_expert, Tensor(c!) num_tiles, Tensor(d!) pair_slot, Tensor(e!)? group_end=None, int expert_lo=0) -> ()");
   m.def("moe_gather(Tensor(a!) out, Tensor x, Tensor slots, int k) -> ()");
   m.def("moe_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor slots, Tensor tile_expert, int tile, int gather_k) -> ()");
   m.def("moe_combine(Tensor(a!) out, Tensor y, Tensor w, Tensor pair_slot, int k) -> ()");

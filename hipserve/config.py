@@ -520,6 +520,10 @@ class EngineConfig:
     num_kv_blocks: int | None = None     # override the memory-derived KV pool size
     enable_prefix_caching: bool = True
     enforce_eager: bool = False
+    # MoE at TP > 1: every rank holds num_experts / TP whole experts instead of a width slice
+    # of each (vLLM's --enable-expert-parallel). Chosen automatically where the width slice
+    # has no gfx950 expert kernel (models.llama.moe_sharding)
+    enable_expert_parallel: bool = False
     cuda_graph_max_bs: int = 256
     seed: int = 0
     trust_remote_code: bool = False

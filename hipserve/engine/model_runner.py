@@ -98,7 +98,13 @@ class ModelRunner:
         self.max_model_len = min(ecfg.max_model_len or mcfg.max_position_embeddings,
                                  mcfg.max_position_embeddings)
         self.block_size = ecfg.block_size
-        self.model = LlamaModel(mcfg, tp, self.device, self.dtype, self.ops, max_pos=self.max_model_len)
+        self.model = LlamaModel(mcfg, tp, self.device, self.dtype, self.ops, max_pos=self.max_model_len,
+                                enable_expert_parallel=ecfg.enable_expert_parallel)
+        if mcfg.num_experts and tp.world_size > 1:
+            m = self.model
+            log.info("rank %d/%d MoE sharding: %s (experts %d-%d of %d, width %d of %d)", tp.rank, tp.world_size,
+                     m.moe_shard[0], m.expert_lo, m.expert_lo + m.num_local_experts - 1, mcfg.num_experts,
+                     m.inter, mcfg.expert_size)
         self.model.decode_partition = ecfg.decode_partition
         self.model.block_size_hint = ecfg.block_size
         if ecfg.kv_fp8:  # e4m3 paged KV cache (the fused qkv -> attention kernel writes bf16 only)

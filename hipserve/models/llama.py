@@ -77,8 +77,8 @@ class LayerWeights:
     wd: torch.Tensor | None = None
     # MoE
     router: torch.Tensor | None = None       # [E, H]
-    w13: torch.Tensor | None = None          # [E, 2*I/TP, H]
-    w2: torch.Tensor | None = None           # [E, H, I/TP]
+    w13: torch.Tensor | None = None          # [E, 2*I/TP, H] ([E/TP, 2*I, H] under expert sharding)
+    w2: torch.Tensor | None = None           # [E, H, I/TP] ([E/TP, H, I])
     moe_packed: tuple | None = None          # (w13 gate/up-interleaved, w2) packed per expert for decode
     # family extras (Qwen2 bias, Qwen3/Gemma-3 per-head q/k norms, Gemma-3 sandwich norms)
     bqkv: torch.Tensor | None = None         # [(nq + 2 nkv) * D / TP]
@@ -104,6 +104,39 @@ def shard_sizes(cfg: ModelConfig, tp: int):
     return nq, nkv, inter, vpad
 
 
+def moe_width_has_kernel(cfg: ModelConfig, tp: int) -> bool:
+    """The gfx950 expert GEMMs (streaming decode, packed grouped prefill, quantised) all
+    need the per-rank expert width to be a multiple of 256 (their K step for w2)."""
+    return cfg.expert_size % tp == 0 and (cfg.expert_size // tp) % 256 == 0
+
+
+def moe_sharding(cfg: ModelConfig, tp: int, enable_ep: bool = False, hip: bool = False, rank: int = 0):
+    """How a TP group of ``tp`` ranks holds the MLP of ``cfg``: ``("width", inter)``, every
+    rank a 1/tp slice of each expert's (or the dense MLP's) width, or ``("expert", lo,
+    n_local)``, rank ``rank`` the whole experts ``lo .. lo + n_local - 1`` (expert
+    parallelism: it computes the (token, expert) pairs it owns and the all-reduce after the
+    MoE block sums the ranks' partial outputs). Expert sharding is chosen by the flag
+    (``enable_ep``, vLLM's --enable-expert-parallel) and, on the HIP ops, by itself where
+    the width slice has no expert kernel (Qwen3-30B-A3B: 768 / tp). Raises ``ValueError``
+    where neither split can run."""
+    E = cfg.num_experts
+    if tp == 1 or not E:
+        return ("width", shard_sizes(cfg, tp)[2])
+    shape = f"{cfg.name}: {E} experts of width {cfg.expert_size}"
+    if enable_ep:
+        if E % tp:
+            raise ValueError(f"--enable-expert-parallel needs num_experts % TP == 0 ({shape}, TP={tp}: "
+                             f"E={E}, tp={tp})")
+        return ("expert", rank * (E // tp), E // tp)
+    if not hip or moe_width_has_kernel(cfg, tp):
+        return ("width", shard_sizes(cfg, tp)[2])
+    if E % tp:
+        raise ValueError(f"{shape} cannot run at TP={tp}: the width slice {cfg.expert_size}/{tp} has no gfx950 "
+                         f"expert kernel (it needs a multiple of 256) and expert parallelism "
+                         f"(--enable-expert-parallel) needs num_experts % TP == 0")
+    return ("expert", rank * (E // tp), E // tp)
+
+
 class LlamaModel(MoEMixin):
     # load FP8 checkpoints natively (e4m3 + scales, ops/quant.py) instead of
     # dequantising them to bf16 at load (weights/safetensors_loader.py)
@@ -124,7 +157,7 @@ class LlamaModel(MoEMixin):
     # an in-launch split-K seam costs more than the kernel boundary it replaces; removed)
 
     def __init__(self, cfg: ModelConfig, tp: TPGroup, device, dtype=torch.bfloat16, ops=None,
-                 max_pos: int | None = None):
+                 max_pos: int | None = None, enable_expert_parallel: bool = False):
         self.cfg = cfg
         self.tp = tp
         self.device = torch.device(device)
@@ -132,6 +165,14 @@ class LlamaModel(MoEMixin):
         self.kv_dtype = dtype  # paged KV cache element (ModelRunner: float8_e4m3fn for --kv-cache-dtype fp8)
         self.ops = ops
         self.nq, self.nkv, self.inter, self.vpad = shard_sizes(cfg, tp.world_size)
+        # MoE experts: a width slice of every expert, or whole experts expert_lo .. expert_lo +
+        # num_local_experts - 1 at full width (moe_sharding); routing always sees all experts
+        self.moe_shard = moe_sharding(cfg, tp.world_size, enable_expert_parallel,
+                                      getattr(ops, "name", "") == "hip", tp.rank)
+        self.expert_lo, self.num_local_experts = 0, cfg.num_experts
+        if self.moe_shard[0] == "expert":
+            _, self.expert_lo, self.num_local_experts = self.moe_shard
+            self.inter = cfg.expert_size
         self.D = cfg.head_dim
         self.scale = cfg.attn_scale or 1.0 / math.sqrt(self.D)
         self.layers: list[LayerWeights] = []
@@ -213,12 +254,17 @@ class LlamaModel(MoEMixin):
                 E, Ig = cfg.num_experts, cfg.expert_size
                 lw.router = new(E, H)
                 fill(lw.router, f"{li}.router", 0, 0, H)
-                lw.w13 = new(E, 2 * I, H)
-                lw.w2 = new(E, H, I)
-                for e in range(E):
-                    fill(lw.w13[e, :I], f"{li}.w1", e * Ig + rank * I, 0, H)
-                    fill(lw.w13[e, I:], f"{li}.w3", e * Ig + rank * I, 0, H)
-                    fill(lw.w2[e], f"{li}.w2", e * H, rank * I, Ig)
+                # expert sharding: whole experts lo .. lo + El - 1 (I == Ig, column 0) instead
+                # of columns rank * I .. of every expert; the same unsharded model either way
+                lo, El = self.expert_lo, self.num_local_experts
+                c0 = 0 if self.moe_shard[0] == "expert" else rank * I
+                lw.w13 = new(El, 2 * I, H)
+                lw.w2 = new(El, H, I)
+                for j in range(El):
+                    e = lo + j
+                    fill(lw.w13[j, :I], f"{li}.w1", e * Ig + c0, 0, H)
+                    fill(lw.w13[j, I:], f"{li}.w3", e * Ig + c0, 0, H)
+                    fill(lw.w2[j], f"{li}.w2", e * H, c0, Ig)
             else:
                 lw.wgu = new(2 * I, H)
                 fill(lw.wgu[:I], f"{li}.gate", rank * I, 0, H)
@@ -316,8 +362,12 @@ class LlamaModel(MoEMixin):
                 return Q.QuantWeight([p for p, _ in parts])
             return torch.cat([d for _, d in parts])
 
+        # expert sharding: a rank holds whole rows of ITS experts, so no cross-rank max
+        # (it would mix the scales of unrelated experts, and the row is complete anyway)
+        ep = self.moe_shard[0] == "expert"
+
         def experts(w, rowpar=False):
-            parts = [q8(w[e], rowpar) for e in range(w.shape[0])]
+            parts = [q8(w[e], rowpar and not ep) for e in range(w.shape[0])]
             if all(p is not None for p, _ in parts) and Q.QuantMoE.supported(parts[0][0].kqt, *w.shape[1:]):
                 return Q.QuantMoE([p for p, _ in parts], kmajor=not rowpar)  # w13: super-chunk major
             return torch.stack([d for _, d in parts])

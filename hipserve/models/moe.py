@@ -1,7 +1,10 @@
 """Sparse mixture-of-experts MLP (Mixtral, Qwen3-MoE, Qwen3-VL-MoE): ``MoEMixin``, the
 MoE half of ``models.llama.LlamaModel``. Per layer: router GEMM -> top-k softmax ->
 expert-sorted row tiles (moe_align) -> w13 expert GEMM with the SiLU-GLU -> w2 expert
-GEMM -> weighted combine; ``moe`` picks among the three kernel paths."""
+GEMM -> weighted combine; ``moe`` picks among the three kernel paths. At TP > 1 a rank
+holds a width slice of every expert or, expert-sharded (``models.llama.moe_sharding``),
+whole experts: routing stays over all experts, moe_align keeps the pairs of the local
+expert range, and the all-reduce after the block sums the ranks' partial outputs."""
 from __future__ import annotations
 
 import logging
@@ -31,6 +34,12 @@ class ExpertWeights:
 
 
 class MoEMixin:
+    # experts this rank holds: all of them, width-sliced (the default), or whole experts
+    # expert_lo .. expert_lo + num_local_experts - 1 (models.llama.moe_sharding). Routing is
+    # over all cfg.num_experts either way; only the local count sizes tiles and buffers
+    expert_lo: int = 0
+    num_local_experts: int = 0
+
     def pack_moe_weights(self, drop_plain: bool = False) -> int:
         """Per-expert packed copies of the MoE weights for the decode expert GEMM
         (``moe_hip``): w13 gate/up-interleaved (SiLU-GLU in the GEMM epilogue), w2
@@ -98,7 +107,7 @@ class MoEMixin:
         """Routing (``_route``) and the expert-sorted slot table padded to whole ``tile``-row
         tiles (moe_align; ``ends``: with its per-expert end offsets output): (weights, slots,
         tile_expert, ntiles, pair_slot, cap), ``cap`` the slot count the buffers are sized to."""
-        E, k = self.cfg.num_experts, self.cfg.num_experts_per_tok
+        E, k = self.num_local_experts, self.cfg.num_experts_per_tok
         P, dev = x.shape[0] * k, x.device
         cap = -(-(P + E * (tile - 1)) // tile) * tile
         w, ids = self._route(x, lw, k)
@@ -107,11 +116,13 @@ class MoEMixin:
         ntiles = torch.empty(1, dtype=torch.int32, device=dev)
         pair_slot = torch.empty(P, dtype=torch.int32, device=dev)
         extra = (torch.empty(E, dtype=torch.int32, device=dev),) if ends else ()
-        torch.ops.hipserve.moe_align(ids, E, tile, slots, tile_expert, ntiles, pair_slot, *extra)
+        # pairs of experts outside [expert_lo, expert_lo + E) (another rank's) take no slot
+        torch.ops.hipserve.moe_align(ids, E, tile, slots, tile_expert, ntiles, pair_slot, *(extra or (None,)),
+                                     self.expert_lo)
         return w, slots, tile_expert, ntiles, pair_slot, cap
 
     def _decode_tile(self, P: int) -> int:  # row tile of the streaming expert GEMMs for P (token, expert) pairs
-        E = self.cfg.num_experts
+        E = self.num_local_experts
         return 16 if P <= 8 * E else 32 if P <= 32 * E else 64
 
     def _combine(self, out: torch.Tensor, y: torch.Tensor, S: int, w, pair_slot, k: int, tail=None):
@@ -122,6 +133,8 @@ class MoEMixin:
         output and the residual in place, returns None."""
         op = torch.ops.hipserve
         if tail is not None:
+            # TP = 1 only: the fused tail reads every pair's row (no skipped pairs)
+            assert self.num_local_experts == self.cfg.num_experts, "moe_combine_add_rmsnorm with expert sharding"
             xn, residual, nw = tail
             op.moe_combine_add_rmsnorm(xn, residual, y, S, w, pair_slot, k, nw, self.cfg.rms_norm_eps)
             return None
@@ -160,7 +173,7 @@ class MoEMixin:
                          and (lw.w13 is not None or lw.moe_packed is not None))
             grouped_ok = self.moe_packed_prefill(lw)
             if kernel_ok and (P <= MOE_KERNEL_MAX_PAIRS or not grouped_ok
-                              or (P <= MOE_KERNEL_MAX_ROWS_PER_EXPERT * cfg.num_experts
+                              or (P <= MOE_KERNEL_MAX_ROWS_PER_EXPERT * self.num_local_experts
                                   and self.moe_prefill_choice(T) == "hip")):
                 return self.moe_hip(x, lw, tail)
             if grouped_ok:
@@ -178,16 +191,17 @@ class MoEMixin:
         order = torch.argsort(flat_idx)
         counts = torch.bincount(flat_idx, minlength=cfg.num_experts).tolist()
         start = 0
+        lo = self.expert_lo
         for e, n in enumerate(counts):
-            if n == 0:
-                continue
             sel = order[start:start + n]
             start += n
+            if n == 0 or not lo <= e < lo + self.num_local_experts:  # expert sharding: this rank's experts only
+                continue
             toks = flat_tok[sel]
-            gu = F.linear(x[toks], lw.w13[e])
+            gu = F.linear(x[toks], lw.w13[e - lo])
             act = torch.empty(n, self.inter, device=x.device, dtype=x.dtype)
             self.ops.silu_and_mul(act, gu)
-            y = F.linear(act, lw.w2[e]).float() * flat_w[sel].unsqueeze(-1)
+            y = F.linear(act, lw.w2[e - lo]).float() * flat_w[sel].unsqueeze(-1)
             out.index_add_(0, toks, y)
         return out.to(x.dtype)
 
@@ -254,7 +268,7 @@ class MoEMixin:
         if self.moe_prefill_path == "packed" and T >= self.moe_packed_from_tokens:
             return "packed"
         if self.moe_prefill_path is None:  # untimed (tests, CPU): the grouped GEMM above the kernel row limit
-            E, k = self.cfg.num_experts, self.cfg.num_experts_per_tok
+            E, k = self.num_local_experts, self.cfg.num_experts_per_tok
             return "packed" if T * k > MOE_KERNEL_MAX_ROWS_PER_EXPERT * E else "hip"
         return "hip"
 
@@ -287,11 +301,12 @@ class MoEMixin:
         if (lw is None or not self._moe_packed_shape_ok() or self.MOE_PACKED_PREFILL != "auto"
                 or getattr(self.ops, "name", "") != "hip" or self.device.type != "cuda" or cfg.num_experts > 128):
             return None
-        E, k, H, I = cfg.num_experts, cfg.num_experts_per_tok, cfg.hidden_size, self.inter
+        # E: the experts this rank holds (all of them unless expert-sharded); the router stays global
+        E, k, H, I = self.num_local_experts, cfg.num_experts_per_tok, cfg.hidden_size, self.inter
         quant = lw.w13 is not None and not isinstance(lw.w13, torch.Tensor)
         if not quant and lw.moe_packed is None and lw.w13 is None:
             return None
-        key = [E, k, H, I, T, quant, "v2"]
+        key = [E, k, H, I, T, quant, "v2"] + ([cfg.num_experts] if E != cfg.num_experts else [])
         hit = TC.get(self.device, "moe_prefill", key)
         if hit is not None:
             self.moe_prefill_path, self.moe_packed_from_tokens = hit["path"], hit["packed_from_tokens"]
@@ -301,7 +316,8 @@ class MoEMixin:
         w13 = (torch.randn(E, 2 * I, H, device=dev, generator=g) * 0.02).to(torch.bfloat16)
         w2 = (torch.randn(E, H, I, device=dev, generator=g) * 0.02).to(torch.bfloat16)
         packed = self._pack_experts(w13, w2)
-        router = (torch.randn(E, H, device=dev, generator=g) * 0.3).to(torch.bfloat16)
+        # routed over all experts, so the local pair counts are those of a real step
+        router = (torch.randn(cfg.num_experts, H, device=dev, generator=g) * 0.3).to(torch.bfloat16)
         syn = ExpertWeights(router, w13, w2, packed)
         counts = []
         t = T
@@ -328,8 +344,8 @@ class MoEMixin:
         if best == "packed" and len(rows) and all(wins):
             frm = 0  # wins down to the pair limit: every prefill-sized batch
         self.moe_prefill_path, self.moe_packed_from_tokens = best, frm
-        r = {"E": E, "H": H, "I": I, "tokens": T, "quant": quant, "path": best, "packed_from_tokens": frm,
-             "timing": rows}
+        r = {"E": E, "E_global": cfg.num_experts, "H": H, "I": I, "tokens": T, "quant": quant, "path": best,
+             "packed_from_tokens": frm, "timing": rows}
         TC.put(self.device, "moe_prefill", key, r)
         TC.flush()
         log.info("MoE prefill expert GEMMs: %s", r)
@@ -346,7 +362,7 @@ class MoEMixin:
         epilogue, and w2 writes split-K fp32 partials that the combine sums."""
         op = torch.ops.hipserve
         cfg = self.cfg
-        E, k, H = cfg.num_experts, cfg.num_experts_per_tok, cfg.hidden_size
+        E, k, H = self.num_local_experts, cfg.num_experts_per_tok, cfg.hidden_size
         T, dev = x.shape[0], x.device
         P = T * k
         tile = self._decode_tile(P)
@@ -388,7 +404,7 @@ class MoEMixin:
         weighted combine). No host synchronisation (graph-capturable)."""
         op = torch.ops.hipserve
         cfg = self.cfg
-        E, k, H = cfg.num_experts, cfg.num_experts_per_tok, cfg.hidden_size
+        E, k, H = self.num_local_experts, cfg.num_experts_per_tok, cfg.hidden_size
         T, dev = x.shape[0], x.device
         P = T * k
         tile = self._decode_tile(P)

@@ -49,6 +49,9 @@ def build_parser(prog="hipserve") -> argparse.ArgumentParser:
     ap.add_argument("--num-kv-blocks", type=int, default=None)
     ap.add_argument("--enable-prefix-caching", action=argparse.BooleanOptionalAction, default=True)
     ap.add_argument("--enforce-eager", action="store_true")
+    ap.add_argument("--enable-expert-parallel", action="store_true",
+                    help="MoE models at TP > 1: whole experts per rank instead of a width slice of each "
+                         "(automatic where the width slice has no expert kernel, e.g. Qwen3-30B-A3B)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--n-gpu-layers", "-ngl", dest="ngl", type=int, default=None,
                     help="accepted for llama-server compatibility (all layers always run on the GPU)")
@@ -75,7 +78,8 @@ def config_from_args(a) -> EngineConfig:
         max_num_batched_tokens=a.max_num_batched_tokens or default_batched_tokens(a.model, a.load_format,
                                                                                    a.quantization),
         num_kv_blocks=a.num_kv_blocks, kv_cache_dtype=getattr(a, "kv_cache_dtype", "auto"),
-        enable_prefix_caching=a.enable_prefix_caching, enforce_eager=a.enforce_eager, seed=a.seed,
+        enable_prefix_caching=a.enable_prefix_caching, enforce_eager=a.enforce_eager,
+        enable_expert_parallel=getattr(a, "enable_expert_parallel", False), seed=a.seed,
         trust_remote_code=a.trust_remote_code, host=a.host, port=a.port,
         extra={"quantization": a.quantization} if a.quantization else {})
 

@@ -307,7 +307,8 @@ def load_hf_weights(model: LlamaModel, model_path: str):
             lw.post_attn_norm = normw(p + "post_attention_layernorm.weight")
             lw.post_ff_norm = normw(p + "post_feedforward_layernorm.weight")
         if cfg.num_experts:
-            lw.router, lw.w13, lw.w2 = _load_experts(ck, p, cfg, r, inter, to, dev if native_fp8 else None)
+            lw.router, lw.w13, lw.w2 = _load_experts(ck, p, cfg, r, inter, to, dev if native_fp8 else None,
+                                                     getattr(model, "moe_shard", None))
         elif ck.has(p + "mlp.gate_up_proj.weight"):  # Phi-3: fused [gate; up]
             f = ck.full(p + "mlp.gate_up_proj.weight")
             I = cfg.intermediate_size
@@ -329,8 +330,9 @@ def load_hf_weights(model: LlamaModel, model_path: str):
         model.visual.load(ck.full, vname[: -len("patch_embed.proj.weight")])
 
 
-def _load_experts(ck, p, cfg, r, inter, to, native_dev=None):
-    """(router [E, H], w13 [E, 2*I/TP, H] as [gate; up], w2 [E, H, I/TP]) from
+def _load_experts(ck, p, cfg, r, inter, to, native_dev=None, shard=None):
+    """(router [E, H], w13 [E, 2*I/TP, H] as [gate; up], w2 [E, H, I/TP]; with ``shard`` =
+    ("expert", lo, n) the whole experts lo .. lo + n - 1: [n, 2*I, H], [n, H, I]) from
     Mixtral (block_sparse_moe.experts.e.w1/w3/w2), Qwen3-MoE
     (mlp.experts.e.gate_proj/up_proj/down_proj) or fused expert tensors
     (mlp.experts.gate_up_proj [E, 2I, H] / Qwen3-VL-MoE's transposed [E, H, 2I]).
@@ -338,7 +340,9 @@ def _load_experts(ck, p, cfg, r, inter, to, native_dev=None):
     reference's AWQ-8bit export) or per-channel FP8 experts stay quantised
     (``QuantMoE`` stacks for the quantised expert GEMM) instead of becoming bf16."""
     E, H, I = cfg.num_experts, cfg.hidden_size, cfg.expert_size
-    sl = slice(r * inter, (r + 1) * inter)
+    sl, ex = slice(r * inter, (r + 1) * inter), range(E)
+    if shard is not None and shard[0] == "expert":  # expert range, full width (INT8 group scales stay whole)
+        sl, ex = slice(0, I), range(shard[1], shard[1] + shard[2])
     if ck.has(p + "block_sparse_moe.gate.weight"):
         m = p + "block_sparse_moe."
         names = ("w1", "w3", "w2")
@@ -347,21 +351,21 @@ def _load_experts(ck, p, cfg, r, inter, to, native_dev=None):
         names = ("gate_proj", "up_proj", "down_proj")
     router = to(ck.full(m + "gate.weight"))
     if native_dev is not None and not ck.has(m + "experts.gate_up_proj"):
-        q = _native_experts(ck, m, names, E, sl, native_dev)
+        q = _native_experts(ck, m, names, ex, sl, native_dev)
         if q is not None:
             return router, q[0], q[1]
     if ck.has(m + "experts.gate_up_proj"):
-        gu = ck.full(m + "experts.gate_up_proj")
-        dn = ck.full(m + "experts.down_proj")
-        if tuple(gu.shape) == (E, H, 2 * I) and (H != 2 * I or cfg.family == "qwen3_moe"):
+        gu = ck.full(m + "experts.gate_up_proj")[ex.start:ex.stop]
+        dn = ck.full(m + "experts.down_proj")[ex.start:ex.stop]
+        if tuple(gu.shape) == (len(ex), H, 2 * I) and (H != 2 * I or cfg.family == "qwen3_moe"):
             gu = gu.transpose(1, 2)
-        if tuple(dn.shape) == (E, I, H) and (H != I or cfg.family == "qwen3_moe"):
+        if tuple(dn.shape) == (len(ex), I, H) and (H != I or cfg.family == "qwen3_moe"):
             dn = dn.transpose(1, 2)
         w13 = torch.cat([gu[:, sl], gu[:, I + sl.start:I + sl.stop]], 1)
         w2 = dn[:, :, sl]
         return router, to(w13), to(w2)
     w13, w2 = [], []
-    for e in range(E):
+    for e in ex:
         ep = f"{m}experts.{e}."
         g = ck.rows(ep + names[0] + ".weight", sl.start, sl.stop)
         u = ck.rows(ep + names[1] + ".weight", sl.start, sl.stop)
@@ -370,8 +374,8 @@ def _load_experts(ck, p, cfg, r, inter, to, native_dev=None):
     return router, to(torch.stack(w13)), to(torch.stack(w2))
 
 
-def _native_experts(ck, m, names, E, sl, dev):
-    """(QuantMoE w13, QuantMoE w2) of per-expert INT8 / per-channel FP8 tensors, or None
+def _native_experts(ck, m, names, ex, sl, dev):
+    """(QuantMoE w13, QuantMoE w2) of the per-expert INT8 / per-channel FP8 tensors of experts ``ex``, or None
     when the experts are another format or a slice would split a scale group."""
     from ..ops import quant as Q
 
@@ -399,14 +403,14 @@ def _native_experts(ck, m, names, E, sl, dev):
 
     try:
         p13, p2 = [], []
-        for e in range(E):
+        for e in ex:
             ep = f"{m}experts.{e}."
             p13.append(build([part(ep + names[0] + ".weight", 0), part(ep + names[1] + ".weight", 0)]))
             p2.append(build([part(ep + names[2] + ".weight", 1)]))
         if int8 and len({p.kqt for p in p13 + p2}) > 1:  # zero points on some experts only: one format
             p13 = [build([part(f"{m}experts.{e}." + names[0] + ".weight", 0),
-                          part(f"{m}experts.{e}." + names[1] + ".weight", 0)], False) for e in range(E)]
-            p2 = [build([part(f"{m}experts.{e}." + names[2] + ".weight", 1)], False) for e in range(E)]
+                          part(f"{m}experts.{e}." + names[1] + ".weight", 0)], False) for e in ex]
+            p2 = [build([part(f"{m}experts.{e}." + names[2] + ".weight", 1)], False) for e in ex]
     except ValueError:
         return None
     if not (Q.QuantMoE.supported(p13[0].kqt, p13[0].N, p13[0].K) and Q.QuantMoE.supported(p2[0].kqt, p2[0].N, p2[0].K)):
