@@ -388,8 +388,16 @@ void launch_t(void* out, long out_stride, float* ws, const void* x, long x_strid
 // without a scale table (FP8, INT8C) fits 128 VGPRs without spills: 4 waves per SIMD
 // instead of 3, a third more weight bytes in flight (the expert stream is bound by the
 // loads in flight, not by its bytes: INT8's 12 % larger chunks ran as fast)
+// GGUF blocks (Q4_0 .. Q6_K) carry a scale table and a dequant FMA per pair: forced to
+// 4 waves per SIMD the 16-slot Q8_0 / Q5_K / Q6_K bodies spill (32 / 128 / 248 bytes of
+// scratch per lane), while Q4_0 / Q4_1 / Q4_K reach 4 waves unforced — so the GGUF formats
+// stay unconstrained (profiles/r7_gguf_moe_resources.md: every instantiation, scratch 0)
+template <int QT, int MT>
+constexpr int qmoe_waves() {
+  return QT <= Q6_K || QT == INT8 ? 1 : MT == 1 ? 4 : 1;
+}
 template <int QT, int MT, int RT, int NWAVES>
-__global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(MT == 1 && QT != INT8 ? 4 : 1)))
+__global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(qmoe_waves<QT, MT>())))
 void qmoe_kernel(unsigned short* __restrict__ out, long out_stride,
                                                           float* __restrict__ ws, const unsigned short* __restrict__ x,
                                                           long x_stride, const unsigned char* __restrict__ q,
@@ -891,6 +899,12 @@ bool launch_qmoe_gemm(void* out, long out_stride, float* ws, const void* x, long
   if (glu && (tile == 64 || S != 1 || ws != nullptr || (N / 2) % 16)) return false;
   const MoeQ moe{slots, tile_expert, w_estride, rs_estride, gather_k, tiles_cap * tile, kmajor ? 1 : 0, glu};
   switch (qtype) {
+    case Q4_0: moe_launch_t<Q4_0>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
+    case Q4_1: moe_launch_t<Q4_1>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
+    case Q8_0: moe_launch_t<Q8_0>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
+    case Q4_K: moe_launch_t<Q4_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
+    case Q5_K: moe_launch_t<Q5_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
+    case Q6_K: moe_launch_t<Q6_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
     case FP8: moe_launch_t<FP8>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
     case INT8: moe_launch_t<INT8>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
     case INT8C: moe_launch_t<INT8C>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;

@@ -423,7 +423,9 @@ int64_t qmoe_gemm(at::Tensor& out, at::Tensor& ws, const at::Tensor& x, const at
                   int64_t qtype, int64_t N, int64_t K, const at::Tensor& slots, const at::Tensor& tile_expert,
                   int64_t tile, int64_t gather_k, int64_t splits, bool kmajor, int64_t glu) {
   CHECK_DEV(x); CHECK_BF16(x); CHECK_ROWMAJOR(x);
-  TORCH_CHECK(qtype == 6 || qtype == 8 || qtype == 9, "qmoe_gemm: expert formats FP8 (per-row scale), INT8, INT8C");
+  // 0-5: GGUF blocks Q4_0, Q4_1, Q8_0, Q4_K, Q5_K, Q6_K (scales inside the blocks, no rs)
+  TORCH_CHECK((qtype >= 0 && qtype <= 6) || qtype == 8 || qtype == 9,
+              "qmoe_gemm: expert formats GGUF Q4_0 / Q4_1 / Q8_0 / Q4_K / Q5_K / Q6_K, FP8 (per-row scale), INT8, INT8C");
   TORCH_CHECK(tile == 16 || tile == 32 || tile == 64, "qmoe_gemm: tile 16/32/64");
   TORCH_CHECK(N % 16 == 0 && K % 256 == 0 && x.size(1) >= K && x.stride(0) % 8 == 0, "qmoe_gemm: shapes");
   TORCH_CHECK(slots.scalar_type() == at::kInt && tile_expert.scalar_type() == at::kInt && slots.is_contiguous() &&

@@ -277,17 +277,33 @@ class LlamaModel(MoEMixin):
 
     # synthetic GGUF schemes (GGUF-tier benchmarks): per projection ggml type;
     # q4_k_m mirrors llama.cpp's Q4_K_M mix (attn_v, ffn_down, output in Q6_K)
+    # (MoE: gate_exps / up_exps / down_exps are the stacked expert tensors' formats)
     QUANT_SCHEMES = {
-        "q4_k_m": {"q": 12, "k": 12, "v": 14, "o": 12, "gate": 12, "up": 12, "down": 14, "output": 14},
-        "q8_0": {n: 8 for n in ("q", "k", "v", "o", "gate", "up", "down", "output")},
-        "q4_0": {**{n: 2 for n in ("q", "k", "v", "o", "gate", "up", "down")}, "output": 14},
+        "q4_k_m": {"q": 12, "k": 12, "v": 14, "o": 12, "gate": 12, "up": 12, "down": 14, "output": 14,
+                   "gate_exps": 12, "up_exps": 12, "down_exps": 14},
+        "q8_0": {n: 8 for n in ("q", "k", "v", "o", "gate", "up", "down", "output", "gate_exps", "up_exps",
+                                "down_exps")},
+        "q4_0": {**{n: 2 for n in ("q", "k", "v", "o", "gate", "up", "down", "gate_exps", "up_exps", "down_exps")},
+                 "output": 14},
     }
+    # distinct random expert stacks generated on the host per (format, shape); further layers
+    # reuse them round-robin (each layer still holds its own device copy)
+    SYNTH_EXPERT_STACKS = 2
 
     def allocate_random_quant(self, scheme: str, seed: int = 0):
         """Random-init model with GGUF-quantised projections (``QuantWeight``, the
         fused dequant-GEMM kernels of csrc/kernels/gguf.hip): random valid ggml
         blocks of each projection's format. Off the GPU the same blocks are
-        dequantised to dense weights (CPU plumbing / numerics oracle)."""
+        dequantised to dense weights (CPU plumbing / numerics oracle).
+
+        MoE configs get a bf16 router and the experts' ``w13`` / ``w2`` in the scheme's
+        ``gate_exps`` / ``up_exps`` / ``down_exps`` formats: ``QuantMoE`` block stacks on
+        the GPU, dense tensors of the same blocks elsewhere. Generating 128 x 48 random
+        expert stacks on the host would dominate the start-up of a 30B model (~17 GB of
+        random bytes plus their repack), so only ``SYNTH_EXPERT_STACKS`` distinct stacks
+        per projection are generated and later layers take copies of them in turn; every
+        layer still owns its bytes in HBM, so decode streams cold weights as with a real
+        file."""
         import numpy as np
 
         from ..weights import gguf as G
@@ -313,17 +329,57 @@ class LlamaModel(MoEMixin):
             return torch.cat([torch.from_numpy(G.dequantize(r, t, n * kk).reshape(n, kk)).to(dt)
                               for t, n, kk, r in raws], 0)
 
+        E, Ie = cfg.num_experts, cfg.expert_size
+        stacks: dict = {}
+
+        def expert_stacks(li):
+            """(w13, w2) of layer ``li``: block stacks only if the expert GEMM takes BOTH (the
+            MoE paths need w13 and w2 of one kind), else both dense."""
+            key = li % self.SYNTH_EXPERT_STACKS
+            if key in stacks:
+                return tuple(w.clone() for w in stacks[key])
+            # (kinds stacked per expert, rows of each kind, K, k-major): w13 super-chunk major
+            specs = [(("gate_exps", "up_exps"), Ie, H, True), (("down_exps",), H, Ie, False)]
+            gen = []
+            for kinds, n, kk, km in specs:
+                ts = [qtype(k, kk) for k in kinds]
+                gen.append((ts, [Q.random_blocks(rng, t, E * n, kk).reshape(E, -1) for t in ts], len(kinds) * n, n, kk, km))
+            blocks = dev.type == "cuda" and all(
+                len(set(ts)) == 1 and all(Q.QuantMoE.supported(Q.KERNEL_QT.get(ts[0], -1), rows, kk, r) for r in raws)
+                for ts, raws, rows, n, kk, km in gen)
+            out = []
+            for ts, raws, rows, n, kk, km in gen:
+                if blocks:
+                    out.append(Q.QuantMoE.from_blocks(raws[0] if len(raws) == 1 else np.concatenate(raws, 1), ts[0], E,
+                                                      rows, kk, dev, kmajor=km))
+                else:
+                    out.append(torch.cat([torch.from_numpy(G.dequantize(r.reshape(-1), t, E * n * kk).reshape(E, n, kk))
+                                          for t, r in zip(ts, raws)], 1).to(device=dev, dtype=dt))
+            stacks[key] = tuple(out)
+            return stacks[key]
+
         g = torch.Generator().manual_seed(seed)
         self.embed = (torch.randn(V, H, generator=g) * 0.02).to(device=dev, dtype=dt)
         self.norm = torch.ones(H, device=dev, dtype=dt)
         self.lm_head = mat(("output", V, H))
         self.layers = []
-        for _ in range(cfg.num_layers):
-            self.layers.append(LayerWeights(
+        for li in range(cfg.num_layers):
+            lw = LayerWeights(
                 ln1=torch.ones(H, device=dev, dtype=dt),
                 wqkv=mat(("q", nq * D, H), ("k", nkv * D, H), ("v", nkv * D, H)),
-                wo=mat(("o", H, nq * D)), ln2=torch.ones(H, device=dev, dtype=dt),
-                wgu=mat(("gate", I, H), ("up", I, H)), wd=mat(("down", H, I))))
+                wo=mat(("o", H, nq * D)), ln2=torch.ones(H, device=dev, dtype=dt))
+            # Qwen3-MoE: per-head q/k norms as in allocate_random. Tied to E on purpose: the
+            # dense qwen3 presets have always run this synthetic path without the norms, and
+            # giving them some would change what their existing benchmark rows measured
+            if cfg.qk_norm and E:
+                lw.q_norm = torch.ones(D, device=dev, dtype=torch.float32)
+                lw.k_norm = torch.ones(D, device=dev, dtype=torch.float32)
+            if E:
+                lw.router = (torch.randn(E, H, generator=g) * 0.02).to(device=dev, dtype=dt)
+                lw.w13, lw.w2 = expert_stacks(li)
+            else:
+                lw.wgu, lw.wd = mat(("gate", I, H), ("up", I, H)), mat(("down", H, I))
+            self.layers.append(lw)
         self.quant_linear = Q.quant_linear
 
     def allocate_random_fp8(self, seed: int = 0, kind: str = "fp8"):

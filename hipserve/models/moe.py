@@ -397,7 +397,9 @@ class MoEMixin:
         return self._combine(out, y, 0, w, pair_slot, k, tail)
 
     def moe_quant(self, x: torch.Tensor, lw, tail=None) -> torch.Tensor | None:
-        """Decode-sized MoE on quantised experts (INT8 / FP8, ``QuantMoE``): routing and
+        """Decode-sized MoE on quantised experts (``QuantMoE``: INT8 / FP8 checkpoints, or
+        the GGUF blocks Q4_0 / Q4_1 / Q8_0 / Q4_K / Q5_K / Q6_K of a MoE GGUF file; w13 and
+        w2 may differ in format, Q4_K_M puts down experts in Q6_K): routing and
         expert-sorted tiles as ``moe_hip``, then the dequant-MFMA expert GEMM in its
         MoE mode (gathered token rows, one expert's weight stream per workgroup) for
         w13, SiLU-GLU, and w2 (split over K into fp32 partials summed by the

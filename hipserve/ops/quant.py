@@ -880,18 +880,25 @@ def make_dense_shadows(weights, device, reserve_bytes: int, gguf: bool = True) -
 class QuantMoE:
     """The quantised experts of one MoE projection, stacked for the expert GEMM
     (``qmoe_gemm``, gguf_mfma.hip MoE mode): ``q`` uint8 [E, N/16 * K/256 * chunk]
-    (each expert in the v2 tiled layout), FP8 row scales ``rs`` [E, N]. INT8
-    (compressed-tensors 8-bit, the reference's AWQ-8bit export) and per-channel FP8
-    experts; prefill runs bf16 expert GEMMs on ``dense`` (a resident shadow when HBM
-    allows, else a per-call dequantised scratch)."""
+    (each expert in the v2 tiled layout), row scales ``rs`` [E, N] for FP8 / INT8C (empty
+    for the formats whose scales sit inside the chunks). Formats: INT8 (compressed-tensors
+    8-bit, the reference's AWQ-8bit export), per-channel FP8, and the GGUF blocks Q4_0 /
+    Q4_1 / Q8_0 / Q4_K / Q5_K / Q6_K (``from_blocks``: a MoE GGUF's ``*_exps`` tensors stay
+    resident as their blocks only). Prefill runs bf16 expert GEMMs on ``dense`` (a resident
+    shadow when asked for, else a per-call dequantised scratch)."""
 
-    KERNEL_QTS = (6, 8, 9)  # FP8 (per-row scale), INT8, INT8C (per-row scale)
+    # GGUF Q4_0 .. Q6_K (scales in the blocks), FP8 (per-row scale), INT8, INT8C (per-row scale)
+    KERNEL_QTS = GGUF_KQT + (6, 8, 9)
 
     def __init__(self, parts: list, kmajor: bool = False):
         p0 = parts[0]
         assert all(p.kqt == p0.kqt and p.N == p0.N and p.K == p0.K and p.tiled for p in parts)
-        self.E, self.N, self.K, self.kqt = len(parts), p0.N, p0.K, p0.kqt
-        self.q = torch.stack([p.q.reshape(-1) for p in parts]).contiguous()
+        rs = torch.stack([p.rs for p in parts]).contiguous() if p0.kqt in (6, 9) else None
+        self._init(torch.stack([p.q.reshape(-1) for p in parts]).contiguous(), p0.kqt, p0.N, p0.K, rs, kmajor)
+
+    def _init(self, q: torch.Tensor, kqt: int, N: int, K: int, rs, kmajor: bool):
+        self.E, self.N, self.K, self.kqt = q.shape[0], N, K, kqt
+        self.q = q
         # kmajor: each expert [K/256][N/16][chunk] instead of [N/16][K/256][chunk] — at a
         # given super-chunk the workgroups of an expert stream one contiguous column of it
         # (w13 at 64 tokens: 84 -> 72 us, profiles/r6_qmoe_int8c_kmajor_bench.log)
@@ -899,9 +906,30 @@ class QuantMoE:
         if self.kmajor:
             G, nsb = self.N // 16, self.K // 256
             self.q = self.q.view(self.E, G, nsb, -1).transpose(1, 2).contiguous().view(self.E, -1)
-        self.rs = (torch.stack([p.rs for p in parts]).contiguous() if p0.kqt in (6, 9)
-                   else torch.empty(0, 0, dtype=torch.float32, device=p0.q.device))
+        self.rs = rs if rs is not None else torch.empty(0, 0, dtype=torch.float32, device=q.device)
         self.dense = None
+
+    @classmethod
+    def from_blocks(cls, raw, qtype: int, E: int, N: int, K: int, device, kmajor: bool = False):
+        """``E`` stacked experts of [N, K] raw ggml blocks of one format (a GGUF
+        ``*_exps`` tensor, ne = [K, N, E], expert-major; for w13 the rows of expert e are
+        [gate_e; up_e]) -> the tiled [E, N/16 * K/256 * chunk] stack. The stacked experts
+        are one tiled [E N, K] matrix, so one ``repack_tiled`` call covers the stack. The
+        blocks carry their own scales: ``rs`` stays empty."""
+        if not cls.supported(KERNEL_QT.get(qtype, -1), N, K):
+            raise ValueError(f"QuantMoE.from_blocks: {G.TYPE_NAMES.get(qtype, qtype)} experts [{N}, {K}] have no "
+                             f"expert kernel (GGUF kernel formats, N % 16 == 0, K % 256 == 0)")
+        tiled = repack_tiled(raw, qtype, E * N, K)  # [E N / 16, K / 256, chunk]
+        self = cls.__new__(cls)
+        self._init(torch.from_numpy(tiled.reshape(E, -1)).to(device), KERNEL_QT[qtype], N, K, None, kmajor)
+        return self
+
+    def clone(self):
+        """The same experts with their own copy of the blocks (no bf16 shadow)."""
+        c = QuantMoE.__new__(QuantMoE)
+        c.__dict__.update(self.__dict__)
+        c.q, c.dense = self.q.clone(), None
+        return c
 
     @property
     def shape(self):
@@ -917,8 +945,15 @@ class QuantMoE:
         return out
 
     @staticmethod
-    def supported(kqt: int, N: int, K: int) -> bool:
-        return kqt in QuantMoE.KERNEL_QTS and N % 16 == 0 and K % 256 == 0
+    def supported(kqt: int, N: int, K: int, raw=None) -> bool:
+        """The expert GEMM takes experts of kernel format ``kqt`` and shape [N, K]; for the
+        GGUF formats with ``raw`` (their ggml blocks) also that every block scale lies in the
+        kernel's subnormal-dequant range (``sub_scale_ok``)."""
+        if kqt not in QuantMoE.KERNEL_QTS or N % 16 or K % 256:
+            return False
+        if raw is not None and kqt in GGUF_KQT:
+            return sub_scale_ok(raw, next(t for t, k in KERNEL_QT.items() if k == kqt))
+        return True
 
 
 _MOE_SCRATCH: dict = {}

@@ -21,11 +21,14 @@ model runs RoPE in "interleaved" mode (rope_mode = 1).
 """
 from __future__ import annotations
 
+import logging
 import os
 import struct
 from dataclasses import dataclass
 
 import numpy as np
+
+log = logging.getLogger(__name__)
 
 GGUF_MAGIC = b"GGUF"
 
@@ -169,22 +172,32 @@ class GGUFFile:
         n_exp = int(g("expert_count", 0) or 0)
         if a not in GGUF_ARCHS:
             raise NotImplementedError(f"GGUF architecture {a!r} (supported: {', '.join(GGUF_ARCHS)})")
+        if int(g("expert_shared_count", 0) or 0):
+            raise NotImplementedError(f"{self.path}: shared experts ({a}.expert_shared_count = "
+                                      f"{int(g('expert_shared_count'))}) are not supported")
+        moe_ffn = int(g("expert_feed_forward_length", 0) or 0)
+        if a == "qwen3moe" and not (n_exp and moe_ffn):
+            raise NotImplementedError(f"{self.path}: qwen3moe needs {a}.expert_count and "
+                                      f"{a}.expert_feed_forward_length")
         if int(g("rope.dimension_count", head_dim) or head_dim) != head_dim:
             raise NotImplementedError("partial rotary embeddings are not supported")
-        fam = {"llama": "mixtral" if n_exp else "llama"}.get(a, a)
+        fam = {"llama": "mixtral" if n_exp else "llama", "qwen3moe": "qwen3_moe"}.get(a, a)
         return ModelConfig(
             name=name or md.get("general.name", os.path.basename(self.path)),
             architecture="mixtral" if n_exp else "llama", family=fam,
             hidden_size=H, num_layers=int(g("block_count")), num_heads=nh,
             num_kv_heads=int(g("attention.head_count_kv", nh)), head_dim=head_dim,
-            intermediate_size=int(g("feed_forward_length")), vocab_size=V,
+            # qwen3moe files may carry no dense feed_forward_length: every layer is sparse
+            intermediate_size=int(g("feed_forward_length", 0) or moe_ffn) if a == "qwen3moe"
+            else int(g("feed_forward_length")), vocab_size=V,
+            moe_intermediate_size=moe_ffn if a == "qwen3moe" else 0,
             rms_norm_eps=float(g("attention.layer_norm_rms_epsilon", 1e-5)),
             # llama.cpp permutes llama q/k rows for interleaved RoPE; phi3 / qwen run NeoX RoPE
             rope_theta=float(g("rope.freq_base", 10000.0)), rope_mode=1 if a == "llama" else 0,
             max_position_embeddings=int(g("context_length", 4096)),
             tie_word_embeddings="output.weight" not in self.tensors,
             num_experts=n_exp, num_experts_per_tok=int(g("expert_used_count", 0) or 0),
-            qkv_bias=a == "qwen2", qk_norm=a == "qwen3",
+            qkv_bias=a == "qwen2", qk_norm=a in ("qwen3", "qwen3moe"),  # norm_topk_prob: the default (True)
             bos_token_id=int(md.get("tokenizer.ggml.bos_token_id", 1)),
             eos_token_id=tuple(sorted(eos_ids)))
 
@@ -319,6 +332,17 @@ def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
         out[:, 0:2] = _to_f16_bytes(d)
         out[:, 2:18] = q[:, :16] | (q[:, 16:] << 4)
         return out.reshape(-1)
+    if qtype == Q5_0:
+        idx = np.abs(xb).argmax(1)
+        mx = xb[np.arange(nb), idx]
+        d = (mx / -16.0).astype(np.float16).astype(np.float32)
+        inv = np.where(d != 0, 1.0 / np.where(d != 0, d, 1), 0)
+        q = np.clip(np.floor(xb * inv[:, None] + 16.5), 0, 31).astype(np.uint32)
+        qh = ((q >> 4) << np.arange(32, dtype=np.uint32)[None, :]).sum(1, dtype=np.uint32)  # bit j: element j
+        out[:, 0:2] = _to_f16_bytes(d)
+        out[:, 2:6] = qh.astype("<u4").view(np.uint8).reshape(nb, 4)
+        out[:, 6:22] = ((q[:, :16] & 0xF) | ((q[:, 16:] & 0xF) << 4)).astype(np.uint8)
+        return out.reshape(-1)
     if qtype in (Q4_K, Q5_K):
         nbits = 4 if qtype == Q4_K else 5
         qmax = (1 << nbits) - 1
@@ -413,7 +437,9 @@ def _w_val(f, v):
 
 def write_gguf(path: str, metadata: dict, tensors: list[tuple[str, np.ndarray, int]],
                alignment: int = 32):
-    """tensors: (name, float32 array [rows, cols] or [n], ggml type)."""
+    """tensors: (name, float32 array [n], [rows, cols] or [experts, rows, cols], ggml
+    type); the ggml dims are the reversed shape (stacked experts: ne = [cols, rows,
+    experts], expert-major in memory, rows quantised block by block along cols)."""
     blobs = []
     for name, arr, qt in tensors:
         a = np.asarray(arr, np.float32)
@@ -635,7 +661,7 @@ class GGUFTokenizer:
 # ------------------------------------------------------------------ loading
 # llama.cpp architectures the GGUF tier serves (the reference's GGUF chart runs
 # TinyLlama (llama) and Phi-3-mini (phi3): ramalama-models/helm-chart/values.yaml:3-19)
-GGUF_ARCHS = ("llama", "phi3", "qwen2", "qwen3")
+GGUF_ARCHS = ("llama", "phi3", "qwen2", "qwen3", "qwen3moe")
 
 
 def gguf_name_map(layer: int) -> dict:
@@ -648,7 +674,10 @@ def gguf_name_map(layer: int) -> dict:
 def load_gguf_weights(model, path: str):
     """Load a GGUF llama model. Matrices in quantised formats are kept quantised
     on the device (``QuantWeight``) for the fused dequant kernels; norms, F32/F16/
-    BF16 matrices and the embedding table become bf16 tensors."""
+    BF16 matrices and the embedding table become bf16 tensors. MoE files (llama with
+    experts = Mixtral, qwen3moe): the router stays bf16 and the stacked ``*_exps`` tensors
+    become ``QuantMoE`` block stacks on the GPU (per layer and projection; bf16 where the
+    expert GEMM does not take the format), dense tensors on CPU."""
     import torch
 
     from ..models.llama import LayerWeights
@@ -672,6 +701,74 @@ def load_gguf_weights(model, path: str):
             return torch.cat([dense(n) for n in names], 0) if len(names) > 1 else dense(names[0])
         return QuantWeight.from_gguf(gf, names, dev)
 
+    # HIPSERVE_GGUF_MOE_NATIVE=0 (A/B): every layer's experts dequantised to bf16 at load
+    native = dev.type == "cuda" and os.environ.get("HIPSERVE_GGUF_MOE_NATIVE", "1") != "0"
+    E = cfg.num_experts
+
+    def expert_info(name, N, K):
+        if name not in gf.tensors:
+            raise NotImplementedError(f"{path}: MoE layer without {name!r}")
+        t = gf.tensors[name]
+        if t.shape != (K, N, E):  # ggml ne order: expert-major in memory, each expert [N, K] rows
+            raise NotImplementedError(f"{path}: {name!r} has ne = {list(t.shape)}, expected {[K, N, E]}")
+        return t
+
+    def fallback_reason(names, infos, K):
+        """Why the expert GEMM cannot take the stack of ``names`` as blocks, or None."""
+        from ..ops.quant import KERNEL_QT, QuantMoE
+
+        rows = sum(i.shape[1] for i in infos)
+        name = lambda t: TYPE_NAMES.get(t, str(t))  # noqa: E731
+        if len({i.type for i in infos}) != 1:
+            return "gate and up differ in format (" + " / ".join(name(i.type) for i in infos) + ")"
+        if not QuantMoE.supported(KERNEL_QT.get(infos[0].type, -1), rows, K):
+            return f"{name(infos[0].type)} [{rows}, {K}] has no expert kernel"
+        if not all(QuantMoE.supported(KERNEL_QT[i.type], rows, K, gf.raw(n)) for i, n in zip(infos, names)):
+            return "block scales beyond the kernel's f16 dequant range"
+        return None
+
+    def experts(names, infos, K, kmajor, blocks):
+        """The stacked experts of ``names`` (w13: gate then up, rows [gate_e; up_e] per
+        expert): a ``QuantMoE`` of the file's blocks (``blocks``), else a dense
+        [E, rows, K] tensor of the model dtype."""
+        from ..ops.quant import QuantMoE
+
+        if blocks:
+            raw = [np.asarray(gf.raw(n)).reshape(E, -1) for n in names]
+            raw = raw[0] if len(raw) == 1 else np.concatenate(raw, 1)
+            return QuantMoE.from_blocks(raw, infos[0].type, E, sum(i.shape[1] for i in infos), K, dev, kmajor=kmajor)
+        mats = [torch.from_numpy(dequantize(gf.raw(n), i.type, i.n_elements).reshape(E, i.shape[1], K))
+                .to(device=dev, dtype=dt) for i, n in zip(infos, names)]
+        return mats[0] if len(mats) == 1 else torch.cat(mats, 1)
+
+    def moe_layer(p):
+        """(router, w13, w2) of layer prefix ``p`` from ffn_gate_inp / ffn_{gate,up,down}_exps.
+        Block experts or bf16 experts is decided for the layer as a whole: the MoE paths take
+        w13 and w2 of one kind, so if either stack needs the bf16 fallback both get it."""
+        for n in gf.tensors:
+            if n.startswith(p) and "_shexp" in n:
+                raise NotImplementedError(f"{path}: shared experts ({n!r}) are not supported")
+        if p + "ffn_gate.0.weight" in gf.tensors:
+            raise NotImplementedError(f"{path}: per-expert tensors ({p + 'ffn_gate.0.weight'!r}, the legacy MoE "
+                                      f"layout) are not supported; re-convert to stacked *_exps tensors")
+        if p + "ffn_gate_inp.weight" not in gf.tensors:
+            raise NotImplementedError(f"{path}: MoE layer without {p + 'ffn_gate_inp.weight'!r}")
+        H, I = cfg.hidden_size, cfg.expert_size
+        n13, n2 = [p + "ffn_gate_exps.weight", p + "ffn_up_exps.weight"], [p + "ffn_down_exps.weight"]
+        i13, i2 = [expert_info(n, I, H) for n in n13], [expert_info(n, H, I) for n in n2]
+        blocks = False
+        if dev.type == "cuda" and not all(i.type in (F32, F16, BF16) for i in i13 + i2):
+            why = [("HIPSERVE_GGUF_MOE_NATIVE=0", "all")] if not native else \
+                [(w, " + ".join(ns)) for ns, w in ((n13, fallback_reason(n13, i13, H)), (n2, fallback_reason(n2, i2, I)))
+                 if w is not None]
+            blocks = not why
+            if why:
+                log.info("GGUF MoE experts %s*_exps: both stacks dequantised to %s at load (%s)", p + "ffn_", dt,
+                         "; ".join(f"{ns}: {w}" for w, ns in why))
+        # w13 super-chunk major like the INT8C experts (QuantMoE kmajor)
+        return (dense(p + "ffn_gate_inp.weight"), experts(n13, i13, H, True, blocks),
+                experts(n2, i2, I, False, blocks))
+
     model.embed = dense("token_embd.weight")
     model.norm = norm("output_norm.weight")
     model.lm_head = matrix("output.weight") if "output.weight" in gf.tensors else model.embed
@@ -682,9 +779,12 @@ def load_gguf_weights(model, path: str):
         # phi3: fused attn_qkv [q; k; v] and ffn_up holding [gate; up] (no ffn_gate)
         qkv = matrix(p + "attn_qkv.weight") if p + "attn_qkv.weight" in gf.tensors else \
             matrix(n["q"], n["k"], n["v"])
-        gu = matrix(n["gate"], n["up"]) if n["gate"] in gf.tensors else matrix(n["up"])
-        lw = LayerWeights(ln1=norm(n["attn_norm"]), wqkv=qkv, wo=matrix(n["o"]), ln2=norm(n["ffn_norm"]),
-                          wgu=gu, wd=matrix(n["down"]))
+        lw = LayerWeights(ln1=norm(n["attn_norm"]), wqkv=qkv, wo=matrix(n["o"]), ln2=norm(n["ffn_norm"]))
+        if E:  # every layer sparse (Mixtral, Qwen3-MoE)
+            lw.router, lw.w13, lw.w2 = moe_layer(p)
+        else:
+            lw.wgu = matrix(n["gate"], n["up"]) if n["gate"] in gf.tensors else matrix(n["up"])
+            lw.wd = matrix(n["down"])
         if cfg.qkv_bias:  # qwen2
             lw.bqkv = torch.cat([dense(p + f"attn_{x}.bias") for x in ("q", "k", "v")]).contiguous()
         if cfg.qk_norm:  # qwen3
@@ -731,5 +831,59 @@ def write_synthetic_llama_gguf(path: str, cfg, qtype: int = Q8_0, seed: int = 0,
         tensors += [(n["attn_norm"], 1 + r(H), F32), (n["q"], r(nq * D, H), k4), (n["k"], r(nkv * D, H), k4),
                     (n["v"], r(nkv * D, H), k6), (n["o"], r(H, nq * D), k4), (n["ffn_norm"], 1 + r(H), F32),
                     (n["gate"], r(I, H), k4), (n["up"], r(I, H), k4), (n["down"], r(H, I), k6)]
+    write_gguf(path, md, tensors)
+    return path
+
+
+def write_synthetic_moe_gguf(path: str, cfg, arch: str = "qwen3moe", qtype: int = Q8_0, seed: int = 0,
+                             std: float = 0.05, mixed_k: bool = False, expert_types: dict | None = None):
+    """Write a random-weight mixture-of-experts GGUF next to ``write_synthetic_llama_gguf``:
+    ``arch`` "llama" (Mixtral-style: llama metadata with expert_count) or "qwen3moe"
+    (per-head q/k norms, expert_feed_forward_length). Every layer is sparse: an F32 router
+    ``ffn_gate_inp`` and the stacked ``ffn_{gate,up,down}_exps`` tensors (ne = [K, N, E]).
+    ``mixed_k`` mimics Q4_K_M: gate / up experts (and q, k, o) in Q4_K, down experts (and
+    attn_v, output) in Q6_K. ``expert_types``: {layer: (gate, up, down) ggml types}
+    overriding the expert formats of single layers."""
+    if arch not in ("llama", "qwen3moe"):
+        raise ValueError(f"write_synthetic_moe_gguf: arch {arch!r} (llama or qwen3moe)")
+    rng = np.random.default_rng(seed)
+    H, I, D = cfg.hidden_size, cfg.expert_size, cfg.head_dim
+    nq, nkv, V, E = cfg.num_heads, cfg.num_kv_heads, cfg.vocab_size, cfg.num_experts
+
+    def r(*s):
+        return (rng.standard_normal(s) * std).astype(np.float32)
+
+    toks = (["<unk>", "<s>", "</s>"] + [f"<0x{b:02X}>" for b in range(256)] + [f"▁w{i}" for i in range(V - 259)])
+    md = {"general.architecture": arch, "general.name": cfg.name,
+          f"{arch}.context_length": cfg.max_position_embeddings, f"{arch}.embedding_length": H,
+          f"{arch}.block_count": cfg.num_layers,
+          # Mixtral: the experts' width IS the feed-forward length
+          f"{arch}.feed_forward_length": I if arch == "llama" else cfg.intermediate_size,
+          f"{arch}.attention.head_count": nq, f"{arch}.attention.head_count_kv": nkv,
+          f"{arch}.attention.key_length": D, f"{arch}.attention.value_length": D,
+          f"{arch}.rope.freq_base": float(cfg.rope_theta), f"{arch}.rope.dimension_count": D,
+          f"{arch}.attention.layer_norm_rms_epsilon": float(cfg.rms_norm_eps),
+          f"{arch}.expert_count": E, f"{arch}.expert_used_count": cfg.num_experts_per_tok,
+          "tokenizer.ggml.model": "llama", "tokenizer.ggml.tokens": toks,
+          "tokenizer.ggml.scores": [float(-i) for i in range(len(toks))],
+          "tokenizer.ggml.token_type": [3 if i < 3 else (6 if 3 <= i < 259 else 1) for i in range(len(toks))],
+          "tokenizer.ggml.bos_token_id": 1, "tokenizer.ggml.eos_token_id": 2}
+    if arch == "qwen3moe":
+        md[f"{arch}.expert_feed_forward_length"] = I
+    k4 = Q4_K if mixed_k else qtype
+    k6 = Q6_K if mixed_k else qtype
+    tensors = [("token_embd.weight", r(V, H), F16), ("output_norm.weight", 1 + r(H), F32),
+               ("output.weight", r(V, H), k6)]
+    for i in range(cfg.num_layers):
+        n, p = gguf_name_map(i), f"blk.{i}."
+        tg, tu, td = (expert_types or {}).get(i, (k4, k4, k6))
+        tensors += [(n["attn_norm"], 1 + r(H), F32), (n["q"], r(nq * D, H), k4), (n["k"], r(nkv * D, H), k4),
+                    (n["v"], r(nkv * D, H), k6), (n["o"], r(H, nq * D), k4), (n["ffn_norm"], 1 + r(H), F32),
+                    # router logits spread enough for a stable top-k under quantised experts
+                    (p + "ffn_gate_inp.weight", r(E, H) * 4, F32),
+                    (p + "ffn_gate_exps.weight", r(E, I, H), tg), (p + "ffn_up_exps.weight", r(E, I, H), tu),
+                    (p + "ffn_down_exps.weight", r(E, H, I), td)]
+        if arch == "qwen3moe":
+            tensors += [(p + "attn_q_norm.weight", 1 + r(D), F32), (p + "attn_k_norm.weight", 1 + r(D), F32)]
     write_gguf(path, md, tensors)
     return path

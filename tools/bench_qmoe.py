@@ -1,11 +1,12 @@
 """Time the quantised expert GEMM (qmoe_gemm, gguf_mfma.hip MoE mode) of one
-Qwen3-30B-A3B MoE layer at decode batch sizes: w13 (gathered token rows) and w2
-(slot rows, split over K), INT8 (per-32-k scale / offset table) vs INT8C (per-channel,
-row scale in the epilogue) vs FP8, at several K splits. Graph-timed over ``--layers``
-distinct layers (their experts exceed the MALL); TB/s counts the bytes of the experts
-that received tokens.
+MoE layer (``--model``: Qwen3-30B-A3B, Mixtral-8x7B) at decode batch sizes: w13 (gathered
+token rows) and w2 (slot rows, split over K), INT8 (per-32-k scale / offset table) vs
+INT8C (per-channel, row scale in the epilogue) vs FP8 vs the GGUF block formats (q4_0,
+q4_1, q8_0, q4_k, q5_k, q6_k: random valid blocks), at several K splits. Graph-timed over
+``--layers`` distinct layers (their experts exceed the MALL); TB/s counts the bytes of the
+experts that received tokens (for GGUF formats: the bytes of their blocks).
 
-    python tools/bench_qmoe.py [--tokens 16,64,128] [--layers 4]
+    python tools/bench_qmoe.py [--tokens 16,64,128] [--layers 4] [--kinds int8c,q4_k,q6_k,q8_0]
 """
 import argparse
 import json
@@ -20,8 +21,22 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_ops import graph_time  # noqa: E402
 
 
+GGUF_KINDS = {"q4_0": 2, "q4_1": 3, "q8_0": 8, "q4_k": 12, "q5_k": 13, "q6_k": 14}  # ggml type ids
+_blocks: dict = {}
+
+
 def experts(E, N, K, kind, dev, g):
     from hipserve.ops import quant as Q
+    if kind in GGUF_KINDS:
+        # one stack of random blocks per shape, generated and repacked on the host once;
+        # the other layers hold their own copies of it (cold all the same)
+        key = (kind, E, N, K)
+        if key not in _blocks:
+            import numpy as np
+
+            raw = Q.random_blocks(np.random.default_rng(len(_blocks)), GGUF_KINDS[kind], E * N, K)
+            _blocks[key] = Q.QuantMoE.from_blocks(raw, GGUF_KINDS[kind], E, N, K, dev)
+        return _blocks[key].clone()
     parts = []
     for _ in range(E):
         wf = torch.randn(N, K, device=dev, generator=g) * 0.02
