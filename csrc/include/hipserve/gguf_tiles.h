@@ -17,7 +17,12 @@ namespace gq {
 // reference's AWQ-8bit / W8A16 exports): the bytes alone, the row scale applied to the
 // fp32 accumulators in the epilogue as for FP8 (11 % fewer bytes than INT8's per-32-k
 // scale / offset table, and the integers enter the MFMA exactly)
-enum { Q4_0 = 0, Q4_1 = 1, Q8_0 = 2, Q4_K = 3, Q5_K = 4, Q6_K = 5, FP8 = 6, FP8B = 7, INT8 = 8, INT8C = 9 };
+// INT4: unsigned 4-bit weights (AutoAWQ gemm / compressed-tensors pack-quantized W4A16)
+// with INT8's group table: per half lane-quarter (32 k) an f16 scale s and an integer zero
+// point z in [0, 15], w = (u - z) * s (compressed-tensors: z = 8 + zero_point). The
+// nibbles sit in Q4_K's qs arrangement, so the same shifts pick them.
+enum { Q4_0 = 0, Q4_1 = 1, Q8_0 = 2, Q4_K = 3, Q5_K = 4, Q6_K = 5, FP8 = 6, FP8B = 7, INT8 = 8, INT8C = 9,
+       INT4 = 10 };
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -71,10 +76,13 @@ struct Raw {
 //   FP8B  FP8 + [16 rows x 2 f32 block scales]                      4224 B
 //   INT8  [4 x 64 lanes x 16 u8][16 rows x 4 g x 2 halves x (f16 scale, f16 offset)]  4608 B
 //   INT8C [4 x 64 lanes x 16 u8]                                    4096 B
+//   INT4  [2 x 64 lanes x 16 u4 pairs][16 rows x 4 g x 2 halves x (f16 scale, f16 offset)]  2560 B
+//         byte b of lane 16 g + c: low nibble k = 64 g + b, high nibble k = 64 g + 32 + b
+//         (Q4_K's qs); table entry (c, g, h) covers k0 = 64 g + 32 h, offset = -(1024 + z)
 template <int QT>
 constexpr int chunk_bytes() {
   return QT == Q4_K ? 2304 : QT == Q5_K ? 2816 : QT == Q6_K ? 3360 : QT == Q8_0 ? 4352 : QT == Q4_0 ? 2304
-       : QT == Q4_1 ? 2560 : QT == FP8 || QT == INT8C ? 4096 : QT == FP8B ? 4224 : 4608;
+       : QT == Q4_1 || QT == INT4 ? 2560 : QT == FP8 || QT == INT8C ? 4096 : QT == FP8B ? 4224 : 4608;
 }
 // formats whose per-row scale (Part::rs) multiplies the accumulators in the epilogue
 template <int QT>
@@ -133,6 +141,12 @@ HS_DEVICE void load_raw(const unsigned char* ch, int g, int c, int lane, Raw& r)
 #pragma unroll
     for (int i = 0; i < 4; ++i) r.v[i] = ld16(ch + 1024 * i + 16 * lane);
     const uint2 so = *reinterpret_cast<const uint2*>(ch + 4096 + 32 * c + 8 * g);  // (sA, oA), (sB, oB)
+    r.s2[0] = so.x;
+    r.s2[1] = so.y;
+  } else if constexpr (QT == INT4) {
+    r.v[0] = ld16(ch + 16 * lane);
+    r.v[1] = ld16(ch + 1024 + 16 * lane);
+    const uint2 so = *reinterpret_cast<const uint2*>(ch + 2048 + 32 * c + 8 * g);  // (sA, oA), (sB, oB)
     r.s2[0] = so.x;
     r.s2[1] = so.y;
   } else if constexpr (QT == FP8 || QT == FP8B || QT == INT8C) {
@@ -236,7 +250,7 @@ struct Dec {
       d6 = h2f(r.h[0]);
     } else if constexpr (QT == FP8 || QT == FP8B || QT == INT8C) {
       fdA = fdB = QT == FP8B ? __builtin_bit_cast(float, r.s2[0]) : 1.f;
-    } else if constexpr (QT == INT8) {  // c = offset (-1024 - 128 - zp), applied before the scale
+    } else if constexpr (QT == INT8 || QT == INT4) {  // c = offset (-1024 - 128 - zp / -1024 - z), applied before the scale
       fdA = h2f(r.s2[0] & 0xFFFF);
       fcA = h2f(r.s2[0] >> 16);
       fdB = h2f(r.s2[1] & 0xFFFF);
@@ -270,7 +284,7 @@ struct Dec {
       // of the lane's scale word (s >> 2)
       d = d6 * (float)(signed char)((r.s2[s >> 2] >> (8 * (2 * (g & 1) + ((s & 3) >> 1)))) & 0xFF);
       c = 0.f;
-    } else if constexpr (QT == INT8) {
+    } else if constexpr (QT == INT8 || QT == INT4) {
       d = s < 4 ? fdA : fdB;
       c = 0.f;
     } else if constexpr (QT == Q4_K || QT == Q5_K || QT == Q8_0) {
@@ -298,6 +312,15 @@ struct Dec {
       const unsigned p0 = (wa & 0x00FF00FFu) | kMagic, p1 = ((wa >> 8) & 0x00FF00FFu) | kMagic;
       const unsigned p2 = (wb & 0x00FF00FFu) | kMagic, p3 = ((wb >> 8) & 0x00FF00FFu) | kMagic;
       return frag(as_h2(p0) + cc, as_h2(p1) + cc, as_h2(p2) + cc, as_h2(p3) + cc);
+    }
+    if constexpr (QT == INT4) {  // u - z, exact: (1024 + u) - (1024 + z)
+      const u32x4 qs[2] = {r.v[0], r.v[1]};
+      const int sh = s < 4 ? 0 : 4;
+      const h2 cc = s < 4 ? cA : cB;
+      unsigned p[4];
+      nib_pairs(word(qs, 2 * (s & 3)), sh, p[0], p[1]);
+      nib_pairs(word(qs, 2 * (s & 3) + 1), sh, p[2], p[3]);
+      return frag(as_h2(p[0]) + cc, as_h2(p[1]) + cc, as_h2(p[2]) + cc, as_h2(p[3]) + cc);
     }
     if constexpr (QT == FP8 || QT == FP8B) {
       // e4m3 -> f16 by moving bits: sign to bit 15, exponent + mantissa to bits 7-13
@@ -449,6 +472,11 @@ struct Dec {
       const unsigned p0 = (wa & 0x00FF00FFu) | kMagic, p1 = ((wa >> 8) & 0x00FF00FFu) | kMagic;
       const unsigned p2 = (wb & 0x00FF00FFu) | kMagic, p3 = ((wb >> 8) & 0x00FF00FFu) | kMagic;
       return frag((as_h2(p0) + cc) * dd, (as_h2(p1) + cc) * dd, (as_h2(p2) + cc) * dd, (as_h2(p3) + cc) * dd);
+    }
+    if constexpr (QT == INT4) {  // (1024 + u + off) * s, as INT8: no scale-range limit
+      const u32x4 qu = __builtin_bit_cast(u32x4, ints(r, g, s));
+      const h2 dd = s < 4 ? dA : dB;
+      return frag(as_h2(qu[0]) * dd, as_h2(qu[1]) * dd, as_h2(qu[2]) * dd, as_h2(qu[3]) * dd);
     }
     const f16x8 q = ints(r, g, s);
     if constexpr (QT == FP8 || QT == INT8C) return q;  // row scale in the epilogue

@@ -114,7 +114,7 @@ bool launch_gguf_prefill(int epi, void* out, long ldo, const void* x16, const fl
 void launch_x_f16_pairs(void* x16, float* rsc, const void* x, long ldx, int M, int K, hipStream_t s);
 // quantised MoE experts (tiled layout per expert, stacked [E][N/16][K/256][chunk]) over
 // moe_align tiles of 16/32/64 slots: out[slot, N] bf16 (S == 1) or ws[S, nslots, N] fp32.
-// qtype: FP8 (rs [E, N]) or INT8 (the checkpoint expert formats). Returns false for an
+// qtype: FP8 (rs [E, N]), INT8 / INT8C or INT4 (the checkpoint expert formats), or a GGUF block format. Returns false for an
 // unsupported tile / qtype.
 bool launch_qmoe_gemm(void* out, long out_stride, float* ws, const void* x, long x_stride, const void* q,
                       const float* rs, int qtype, long w_estride, long rs_estride, const int* slots,

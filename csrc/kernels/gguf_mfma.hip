@@ -392,9 +392,10 @@ void launch_t(void* out, long out_stride, float* ws, const void* x, long x_strid
 // 4 waves per SIMD the 16-slot Q8_0 / Q5_K / Q6_K bodies spill (32 / 128 / 248 bytes of
 // scratch per lane), while Q4_0 / Q4_1 / Q4_K reach 4 waves unforced — so the GGUF formats
 // stay unconstrained (profiles/r7_gguf_moe_resources.md: every instantiation, scratch 0)
+// INT4 carries INT8's table with Q4_1's bytes: unconstrained like both (profiles/int4_resources.md)
 template <int QT, int MT>
 constexpr int qmoe_waves() {
-  return QT <= Q6_K || QT == INT8 ? 1 : MT == 1 ? 4 : 1;
+  return QT <= Q6_K || QT == INT8 || QT == INT4 ? 1 : MT == 1 ? 4 : 1;
 }
 template <int QT, int MT, int RT, int NWAVES>
 __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(qmoe_waves<QT, MT>())))
@@ -834,6 +835,7 @@ int gguf_tiled_chunk_bytes(int qtype) {
     case FP8B: return chunk_bytes<FP8B>();
     case INT8: return chunk_bytes<INT8>();
     case INT8C: return chunk_bytes<INT8C>();
+    case INT4: return chunk_bytes<INT4>();
   }
   return 0;
 }
@@ -886,6 +888,7 @@ void launch_gguf_gemm_parts(void* out, long out_stride, float* ws, const void* x
       case FP8B: launch_t<FP8B, FP8B>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
       case INT8: launch_t<INT8, INT8>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
       case INT8C: launch_t<INT8C, INT8C>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
+      case INT4: launch_t<INT4, INT4>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
     }
   }
 }
@@ -908,6 +911,7 @@ bool launch_qmoe_gemm(void* out, long out_stride, float* ws, const void* x, long
     case FP8: moe_launch_t<FP8>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
     case INT8: moe_launch_t<INT8>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
     case INT8C: moe_launch_t<INT8C>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
+    case INT4: moe_launch_t<INT4>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
   }
   return false;
 }
@@ -995,6 +999,7 @@ void launch_gguf_dequant_tiled(void* out, const void* q, const float* rs, int qt
     case FP8B: dequant_tiled_kernel<FP8B><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
     case INT8: dequant_tiled_kernel<INT8><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
     case INT8C: dequant_tiled_kernel<INT8C><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
+    case INT4: dequant_tiled_kernel<INT4><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
   }
 }
 

@@ -469,8 +469,8 @@ def default_batched_tokens(model: str, load_format: str = "auto", quantization: 
     7,607 / 432 ms (profiles/r5_bench_8b_chunk16k.json, r5_bench_8b_chunk4k.json)."""
     if quantization is None:
         quantization = checkpoint_quantization(model)
-    if quantization == "int8":
-        return 32768
+    if quantization in ("int8", "int4"):  # int4: the explicit flag only (checkpoint_quantization
+        return 32768                      # reports no 4-bit kind: auto-detected ones keep 8192, unmeasured)
     gguf = quantization in GGUF_QUANTS or load_format == "gguf" or str(model).lower().endswith(".gguf")
     return 16384 if gguf else 8192
 

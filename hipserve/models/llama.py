@@ -308,7 +308,7 @@ class LlamaModel(MoEMixin):
 
         from ..weights import gguf as G
 
-        if scheme.lower() in ("fp8", "int8"):
+        if scheme.lower() in ("fp8", "int8", "int4"):
             return self.allocate_random_fp8(seed, scheme.lower())
         if self.tp.world_size != 1:
             raise NotImplementedError("the GGUF tier runs TP=1 (one device per pod, like llama-server)")
@@ -386,7 +386,11 @@ class LlamaModel(MoEMixin):
         """Random-init model whose projections are 8-bit weights with per-output-channel
         scales, kept native in HBM (ops/quant.py): ``fp8`` = e4m3 (the layout of the
         reference's "FP8-Dynamic" checkpoints), ``int8`` = symmetric int8 weight-only
-        (the reference's AWQ-8bit export). MoE experts become ``QuantMoE`` stacks for
+        (the reference's AWQ-8bit export), ``int4`` = 4-bit group-128 asymmetric weights
+        (the AutoAWQ gemm / compressed-tensors W4A16 layout, INT4 chunks: uniform random
+        nibbles and zero points, one scale giving |w| ~ 0.02, all derived from the
+        position-keyed random weights so every TP degree holds the same model). MoE
+        experts become ``QuantMoE`` stacks for
         the quantised expert GEMM. Embeddings, norms, router and lm_head stay bf16 (the
         checkpoints' ``ignore`` list). Off the GPU the same 8-bit values are
         dequantised to dense weights."""
@@ -398,6 +402,17 @@ class LlamaModel(MoEMixin):
             # expert w2 at TP > 1) takes the max over the ranks' K slices, so every TP
             # degree quantises the same model as TP = 1 (a sharded checkpoint's scale)
             wf = w.float()
+            if kind == "int4":
+                N, K = wf.shape
+                G = 128 if K % 128 == 0 else 32 if K % 32 == 0 else K
+                # the uniform weights of allocate_random (|w| <= 0.02 sqrt(3)) -> uniform nibbles;
+                # a group's zero point is its first nibble (random in 0..15, the same on every rank)
+                u = torch.round((wf / (0.02 * math.sqrt(3.0)) + 1.0) * 7.5).clamp_(0, 15)
+                z = u[:, ::G].contiguous()
+                s = torch.full_like(z, 0.00375).half().float()  # E|u - z| ~ 5.3: |w| ~ 0.02
+                dense = ((u - z.repeat_interleave(G, 1)) * s.repeat_interleave(G, 1)).to(self.dtype)
+                ok = dev.type == "cuda" and N % 16 == 0 and K % 256 == 0 and G % 32 == 0
+                return (Q.QuantPart.from_int4(u.to(torch.uint8), s, z, dev) if ok else None), dense
             amax = wf.abs().amax(1, keepdim=True)
             if rowpar and self.tp.world_size > 1:
                 amax = self.tp.max_(amax)

@@ -32,8 +32,12 @@ INT8 = 1002
 # per-channel symmetric 8-bit (one scale per row, no zero point): the bytes alone in the
 # tiled layout, the scale as the fp32 row scale ``rs`` (gguf_tiles.h INT8C)
 INT8C = 1003
+# 4-bit integer weight-only (AutoAWQ gemm / compressed-tensors pack-quantized W4A16):
+# unsigned nibbles u, per-group f16 scale and integer zero point z in [0, 15]:
+# w = (u - z) * s (gguf_tiles.h INT4)
+INT4 = 1004
 KERNEL_QT = {G.Q4_0: 0, G.Q4_1: 1, G.Q8_0: 2, G.Q4_K: 3, G.Q5_K: 4, G.Q6_K: 5, FP8: 6, FP8B: 7, INT8: 8,
-             INT8C: 9}
+             INT8C: 9, INT4: 10}
 MAX_FUSED_M = 64
 # the W8A8 FP8 decode GEMM (fp8_decode.hip) also takes the decode graph buckets above 64
 # rows (up to 256, max_num_seqs' default): one weight stream per step instead of the
@@ -78,7 +82,7 @@ def repack(raw: np.ndarray, qtype: int, N: int, K: int):
 
 
 CHUNK_BYTES = {G.Q4_K: 2304, G.Q5_K: 2816, G.Q6_K: 3360, G.Q8_0: 4352, G.Q4_0: 2304, G.Q4_1: 2560,
-               FP8: 4096, FP8B: 4224, INT8: 4608, INT8C: 4096}
+               FP8: 4096, FP8B: 4224, INT8: 4608, INT8C: 4096, INT4: 2560}
 
 
 def _lanes(a: np.ndarray, n_ld: int) -> np.ndarray:
@@ -201,6 +205,40 @@ class QuantPart:
         meta = torch.stack([s16, o16], -1).reshape(R, 16, nsb, 8, 2).permute(0, 2, 1, 3, 4).contiguous()
         chunk = torch.cat([lanes, meta.view(torch.uint8).reshape(R, nsb, 512)], 2).contiguous()
         return cls(INT8, N, K, chunk, _E16(device), _E16(device), 0, tiled=True)
+
+    @classmethod
+    def from_int4(cls, u: torch.Tensor, scale: torch.Tensor, zero: torch.Tensor | None, device):
+        """4-bit weight-only matrix: ``u`` [N, K] uint8 in [0, 15], ``scale`` [N, K / group]
+        or [N, 1] (per channel), ``zero`` integer zero points in [0, 15] of the same shape
+        (None: 8, the symmetric compressed-tensors case; AWQ's qzeros as they are):
+        w = (u - zero) * scale, scales held as f16. Groups of a multiple of 32 k;
+        N % 16 == 0, K % 256 == 0. The chunks stay 4-bit (gguf_tiles.h INT4)."""
+        N, K = u.shape
+        if N % 16 or K % 256:
+            raise ValueError(f"int4 weight [{N}, {K}] not supported (needs N % 16 == 0 and K % 256 == 0)")
+        u = u.to(device=device, dtype=torch.uint8)
+        sc = scale.to(device=device, dtype=torch.float32).reshape(N, -1)
+        ng = sc.shape[1]
+        G = K // ng
+        if G * ng != K or G < 32 or G % 32:
+            raise ValueError(f"int4 group size {K}/{ng} not supported (needs a multiple of 32)")
+        z = (zero.to(device=device, dtype=torch.float32).reshape(N, -1) if zero is not None
+             else torch.full_like(sc, 8.0))
+        if z.shape != sc.shape:
+            raise ValueError(f"int4 zero points {tuple(z.shape)} do not match the scales {tuple(sc.shape)}")
+        R, nsb = N // 16, K // 256
+        # byte b of lane (g, c): low nibble k = 64 g + b, high nibble k = 64 g + 32 + b (Q4_K's qs)
+        h = u.reshape(R, 16, nsb, 4, 2, 32)
+        byt = h[:, :, :, :, 0] | (h[:, :, :, :, 1] << 4)                # [R, 16 c, nsb, 4 g, 32]
+        lanes = byt.reshape(R, 16, nsb, 4, 2, 16).permute(0, 2, 4, 3, 1, 5).reshape(R, nsb, 2048)
+        # (scale, offset = -(1024 + z)) per (row, super-chunk, lane quarter g, half h): INT8's table
+        k0 = torch.arange(nsb * 8, device=device) * 32
+        gi = k0 // G
+        s16 = sc[:, gi].to(torch.float16)
+        o16 = (-(1024.0 + z[:, gi])).to(torch.float16)
+        meta = torch.stack([s16, o16], -1).reshape(R, 16, nsb, 8, 2).permute(0, 2, 1, 3, 4).contiguous()
+        chunk = torch.cat([lanes, meta.view(torch.uint8).reshape(R, nsb, 512)], 2).contiguous()
+        return cls(INT4, N, K, chunk, _E16(device), _E16(device), 0, tiled=True)
 
     @classmethod
     def from_fp8(cls, q: torch.Tensor, scale: torch.Tensor, device):
@@ -882,13 +920,14 @@ class QuantMoE:
     (``qmoe_gemm``, gguf_mfma.hip MoE mode): ``q`` uint8 [E, N/16 * K/256 * chunk]
     (each expert in the v2 tiled layout), row scales ``rs`` [E, N] for FP8 / INT8C (empty
     for the formats whose scales sit inside the chunks). Formats: INT8 (compressed-tensors
-    8-bit, the reference's AWQ-8bit export), per-channel FP8, and the GGUF blocks Q4_0 /
+    8-bit, the reference's AWQ-8bit export), INT4 (AutoAWQ gemm / compressed-tensors 4-bit),
+    per-channel FP8, and the GGUF blocks Q4_0 /
     Q4_1 / Q8_0 / Q4_K / Q5_K / Q6_K (``from_blocks``: a MoE GGUF's ``*_exps`` tensors stay
     resident as their blocks only). Prefill runs bf16 expert GEMMs on ``dense`` (a resident
     shadow when asked for, else a per-call dequantised scratch)."""
 
-    # GGUF Q4_0 .. Q6_K (scales in the blocks), FP8 (per-row scale), INT8, INT8C (per-row scale)
-    KERNEL_QTS = GGUF_KQT + (6, 8, 9)
+    # GGUF Q4_0 .. Q6_K (scales in the blocks), FP8 (per-row scale), INT8, INT8C (per-row scale), INT4
+    KERNEL_QTS = GGUF_KQT + (6, 8, 9, 10)
 
     def __init__(self, parts: list, kmajor: bool = False):
         p0 = parts[0]

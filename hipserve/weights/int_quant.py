@@ -1,5 +1,5 @@
-"""Integer weight-only checkpoints (AWQ / GPTQ-style group quantisation), dequantised
-to the compute dtype at load.
+"""Integer weight-only checkpoints (AWQ / GPTQ-style group quantisation): the packings,
+and their dequantisation to the compute dtype for what is not kept quantised in HBM.
 
 The reference's HF chart serves ``cpatonn/Qwen3-VL-30B-A3B-Instruct-AWQ-8bit``
 (vllm-models/helm-chart/values.yaml:8-12): an llm-compressor export in the
@@ -20,9 +20,22 @@ compressed-tensors ``pack-quantized`` format. Two on-disk layouts are read:
 On the GPU, 8-bit pack-quantized dense projections are NOT dequantised: the loader
 (safetensors_loader.py ``int8_part``) keeps the bytes, group scales and zero points
 and the v2 quantised decode GEMM (csrc/kernels/gguf_mfma.hip, INT8 format) dequantises
-in registers — half the bf16 bytes per decode step. 4-bit layouts, AutoAWQ and MoE
-expert weights are dequantised here to bf16 at load (288 GB of HBM holds a 30B-A3B
-model in bf16 several times over).
+in registers — half the bf16 bytes per decode step. Per-expert 8-bit tensors stay
+quantised the same way (``QuantMoE``).
+
+4-bit layouts stay 4-bit as well (``int4_part``, the INT4 kernel format: tiled nibbles +
+a per-32-k f16 scale / zero-point table, 5 bits per weight in HBM): compressed-tensors
+pack-quantized with ``num_bits: 4`` (symmetric: zero 8; asymmetric: 8 + zero_point) and
+AutoAWQ — the latter only when ``quantization_config.quant_method`` is ``awq`` and
+``version`` is ``gemm`` (any letter case, or absent); a ``.qweight`` tensor under any
+other config (GPTQ, AWQ ``gemv``) is not taken for it. Dense q/k/v, o, gate/up, down and
+per-expert projections take that path; a projection whose shape, group (no multiple of
+32) or TP slice (a K slice that splits a group) the kernel cannot take is dequantised
+here to bf16 on its own, as are Phi-3's fused qkv / gate_up, the fused Qwen3-VL expert
+tensors, ``lm_head`` and the embeddings. ``HIPSERVE_INT4_NATIVE=0`` dequantises every
+4-bit tensor here at load (A/B runs). Not measured: gateway throughput of an INT4
+model, TP > 1 on separate devices; auto-detected 4-bit checkpoints keep the default
+8,192-token prefill budget (``config.checkpoint_quantization`` reports no 4-bit kind).
 """
 from __future__ import annotations
 

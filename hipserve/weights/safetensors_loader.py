@@ -12,11 +12,17 @@ network is reachable.
 from __future__ import annotations
 
 import json
+import logging
 import os
 
 import torch
 
 from ..models.llama import LayerWeights, LlamaModel
+
+log = logging.getLogger("hipserve.loader")
+# HIPSERVE_INT4_NATIVE=0: 4-bit AWQ / compressed-tensors weights are dequantised to bf16 at
+# load (the behaviour before the INT4 kernel format), for A/B runs
+INT4_NATIVE = os.environ.get("HIPSERVE_INT4_NATIVE", "1") != "0"
 
 
 def resolve_checkpoint_dir(model: str) -> str:
@@ -55,6 +61,7 @@ class _Ckpt:
         # integer weight-only checkpoints (weights/int_quant.py): "<x>.weight" is a
         # virtual tensor dequantised from "<x>.weight_packed" / "<x>.qweight"
         self.bits = _quant_bits(path)
+        self.qcfg = _quant_config(path)
         self.virtual = {}
         for k in list(self.where):
             for suf, kind in ((".weight_packed", "ct"), (".qweight", "awq")):
@@ -148,6 +155,59 @@ class _Ckpt:
         cs = slice(start // G, stop // G) if scale.shape[1] > 1 else slice(0, 1)
         return u[:, start:stop], scale[:, cs], (zp[:, cs] if zp is not None else None)
 
+    # ---- native 4-bit integer weight-only: compressed-tensors pack-quantized (4 bits) and
+    # AutoAWQ gemm. A ".qweight" tensor alone does not make a checkpoint AWQ here: GPTQ and
+    # AWQ gemv files carry the same names in other packings and stay on the dequantise path
+    def is_int4(self, name) -> bool:
+        kind = self.virtual.get(name, (None,))[0]
+        if kind == "ct":
+            return self.bits == 4
+        if kind == "awq":
+            q = self.qcfg
+            return (str(q.get("quant_method", "")).lower() == "awq" and self.bits in (None, 4)
+                    and str(q.get("version") or "gemm").lower() == "gemm")
+        return False
+
+    def int4_part(self, name, axis: int, start: int, stop: int):
+        """(unsigned nibbles u [rows, cols] uint8, scale [rows, groups], integer zero point
+        in [0, 15] of the same shape or None for 8) of rows / columns [start, stop):
+        w = (u - zero) * scale. None when a column slice would split a group."""
+        from . import int_quant
+
+        kind, base = self.virtual[name]
+        if kind == "awq":
+            u = int_quant._awq_unpack(self._get(base + ".qweight")).t()       # [N, K]
+            zero = int_quant._awq_unpack(self._get(base + ".qzeros")).t().float()  # [N, K / group]
+            scale = self._get(base + ".scales").float().t()
+            N, K = u.shape
+        else:
+            packed = self._get(base + ".weight_packed")
+            scale = self._get(base + ".weight_scale").float()
+            zp = self._get(base + ".weight_zero_point")
+            shp = self._get(base + ".weight_shape")
+            N = packed.shape[0]
+            K = int(shp.reshape(-1)[1]) if shp is not None else packed.shape[1] * 8
+            u = int_quant._unpack_rows(packed, 4, K)  # stored as q + 8
+            if scale.dim() == 1:
+                scale = scale.reshape(-1, 1)
+            zero = None
+            if zp is not None:
+                if zp.dtype == torch.int32 and zp.shape[0] != N:  # packed along N, stored as zp + 8
+                    zero = int_quant._unpack_rows(zp.t().contiguous(), 4, N).t().float()
+                else:
+                    zero = zp.float().reshape(N, -1) + 8.0
+        u = u.to(torch.uint8)
+        if axis == 0:
+            return (u[start:stop].contiguous(), scale[start:stop].contiguous(),
+                    zero[start:stop].contiguous() if zero is not None else None)
+        ng = scale.shape[1]
+        G = K // ng
+        if ng > 1 and (start % G or stop % G):
+            return None
+        cs = slice(start // G, stop // G) if ng > 1 else slice(0, 1)
+        return (u[:, start:stop].contiguous(), scale[:, cs].contiguous(),
+                zero[:, cs].contiguous() if zero is not None else None)
+
     def _is_fp8(self, name) -> bool:
         """True for every tensor that must be dequantised whole before slicing."""
         if name in self.virtual:
@@ -180,6 +240,15 @@ class _Ckpt:
                 s = s.repeat_interleave(bn, 0)[: w.shape[0]].repeat_interleave(bk, 1)[:, : w.shape[1]]
                 return w * s
         raise ValueError(f"FP8 tensor {name} without weight_scale / weight_scale_inv")
+
+
+def _quant_config(path: str) -> dict:
+    """config.json's ``quantization_config`` ({} if absent or unreadable)."""
+    try:
+        with open(os.path.join(path, "config.json")) as f:
+            return json.load(f).get("quantization_config") or {}
+    except (OSError, ValueError):
+        return {}
 
 
 def _quant_bits(path: str) -> int | None:
@@ -227,9 +296,12 @@ def load_hf_weights(model: LlamaModel, model_path: str):
     # native FP8 projections (the FP8-Dynamic / block-FP8 checkpoints, e4m3 + scales)
     # and 8-bit integer weight-only projections (compressed-tensors pack-quantized,
     # the reference's AWQ-8bit export) stay quantised in HBM and are multiplied by
-    # the v2 dequant-MFMA kernel (ops/quant.py): half the bytes of bf16 weights
+    # the v2 dequant-MFMA kernel (ops/quant.py): half the bytes of bf16 weights; 4-bit
+    # AWQ gemm / compressed-tensors projections stay 4-bit the same way (INT4 format)
     native_fp8 = dev.type == "cuda" and getattr(model, "native_fp8", True)
+    native_int4 = native_fp8 and INT4_NATIVE
     n_fp8 = [0]
+    n_int4 = [0, 0, 0]  # projections, expert stacks, resident bytes
 
     def proj(specs):
         """specs: [(name, axis, start, stop)] stacked along the output rows."""
@@ -250,6 +322,20 @@ def load_hf_weights(model: LlamaModel, model_path: str):
                     and (pp[0].shape[1] // pp[1].shape[1]) % 32 == 0 for pp in parts):
                 n_fp8[0] += 1
                 return Q.QuantWeight([Q.QuantPart.from_int8(u, sc, zp, dev) for u, sc, zp in parts])
+        if native_int4 and all(ck.is_int4(n) for n, *_ in specs):
+            from ..ops import quant as Q
+
+            parts = [ck.int4_part(n, ax, a, b) for n, ax, a, b in specs]
+            # a split group, or a shape / group the kernel does not take: bf16 for this projection
+            if all(pp is not None for pp in parts) and all(
+                    pp[0].shape[0] % 16 == 0 and pp[0].shape[1] % 256 == 0
+                    and pp[0].shape[1] % pp[1].shape[1] == 0
+                    and (pp[0].shape[1] // pp[1].shape[1]) % 32 == 0 for pp in parts):
+                w = Q.QuantWeight([Q.QuantPart.from_int4(u, sc, z, dev) for u, sc, z in parts])
+                n_fp8[0] += 1
+                n_int4[0] += 1
+                n_int4[2] += w.nbytes
+                return w
         ts = [ck.rows(n, a, b) if ax == 0 else ck.cols(n, a, b) for n, ax, a, b in specs]
         return to(torch.cat(ts, 0) if len(ts) > 1 else ts[0])
 
@@ -308,7 +394,11 @@ def load_hf_weights(model: LlamaModel, model_path: str):
             lw.post_ff_norm = normw(p + "post_feedforward_layernorm.weight")
         if cfg.num_experts:
             lw.router, lw.w13, lw.w2 = _load_experts(ck, p, cfg, r, inter, to, dev if native_fp8 else None,
-                                                     getattr(model, "moe_shard", None))
+                                                     getattr(model, "moe_shard", None), int4=native_int4)
+            for w in (lw.w13, lw.w2):
+                if getattr(w, "kqt", None) == 10:
+                    n_int4[1] += 1
+                    n_int4[2] += w.q.numel()
         elif ck.has(p + "mlp.gate_up_proj.weight"):  # Phi-3: fused [gate; up]
             f = ck.full(p + "mlp.gate_up_proj.weight")
             I = cfg.intermediate_size
@@ -323,6 +413,9 @@ def load_hf_weights(model: LlamaModel, model_path: str):
         from ..ops import quant as Q
 
         model.quant_linear = Q.quant_linear
+    if n_int4[0] or n_int4[1]:
+        log.info("rank %d/%d: %d projections and %d expert stacks resident as tiled 4-bit chunks only "
+                 "(INT4, %.3f GiB)", r, W, n_int4[0], n_int4[1], n_int4[2] / 2**30)
     if model.visual is not None:  # Qwen3-VL vision tower (bf16 in every checkpoint, replicated)
         vname = ck.find("patch_embed.proj.weight")
         if vname is None:
@@ -330,15 +423,16 @@ def load_hf_weights(model: LlamaModel, model_path: str):
         model.visual.load(ck.full, vname[: -len("patch_embed.proj.weight")])
 
 
-def _load_experts(ck, p, cfg, r, inter, to, native_dev=None, shard=None):
+def _load_experts(ck, p, cfg, r, inter, to, native_dev=None, shard=None, int4=True):
     """(router [E, H], w13 [E, 2*I/TP, H] as [gate; up], w2 [E, H, I/TP]; with ``shard`` =
     ("expert", lo, n) the whole experts lo .. lo + n - 1: [n, 2*I, H], [n, H, I]) from
     Mixtral (block_sparse_moe.experts.e.w1/w3/w2), Qwen3-MoE
     (mlp.experts.e.gate_proj/up_proj/down_proj) or fused expert tensors
     (mlp.experts.gate_up_proj [E, 2I, H] / Qwen3-VL-MoE's transposed [E, H, 2I]).
     With ``native_dev`` (a GPU), per-expert INT8 (compressed-tensors 8-bit, the
-    reference's AWQ-8bit export) or per-channel FP8 experts stay quantised
-    (``QuantMoE`` stacks for the quantised expert GEMM) instead of becoming bf16."""
+    reference's AWQ-8bit export), per-channel FP8 or (with ``int4``) 4-bit AWQ gemm /
+    compressed-tensors experts stay quantised (``QuantMoE`` stacks for the quantised
+    expert GEMM) instead of becoming bf16."""
     E, H, I = cfg.num_experts, cfg.hidden_size, cfg.expert_size
     sl, ex = slice(r * inter, (r + 1) * inter), range(E)
     if shard is not None and shard[0] == "expert":  # expert range, full width (INT8 group scales stay whole)
@@ -351,7 +445,7 @@ def _load_experts(ck, p, cfg, r, inter, to, native_dev=None, shard=None):
         names = ("gate_proj", "up_proj", "down_proj")
     router = to(ck.full(m + "gate.weight"))
     if native_dev is not None and not ck.has(m + "experts.gate_up_proj"):
-        q = _native_experts(ck, m, names, ex, sl, native_dev)
+        q = _native_experts(ck, m, names, ex, sl, native_dev, int4)
         if q is not None:
             return router, q[0], q[1]
     if ck.has(m + "experts.gate_up_proj"):
@@ -374,23 +468,33 @@ def _load_experts(ck, p, cfg, r, inter, to, native_dev=None, shard=None):
     return router, to(torch.stack(w13)), to(torch.stack(w2))
 
 
-def _native_experts(ck, m, names, ex, sl, dev):
-    """(QuantMoE w13, QuantMoE w2) of the per-expert INT8 / per-channel FP8 tensors of experts ``ex``, or None
-    when the experts are another format or a slice would split a scale group."""
+def _native_experts(ck, m, names, ex, sl, dev, int4=True):
+    """(QuantMoE w13, QuantMoE w2) of the per-expert INT8 / INT4 / per-channel FP8 tensors of experts ``ex``,
+    or None when the experts are another format or a slice would split a scale group."""
     from ..ops import quant as Q
 
-    first = f"{m}experts.0.{names[0]}.weight"
+    first = f"{m}experts.{ex[0] if len(ex) else 0}.{names[0]}.weight"
     int8 = ck.is_int8_ct(first)
-    if not int8 and not ck.is_fp8_e4m3(first):
+    i4 = int4 and not int8 and ck.is_int4(first)
+    if not int8 and not i4 and not ck.is_fp8_e4m3(first):
         return None
 
     def part(name, axis):
-        pp = ck.int8_part(name, axis, sl.start, sl.stop) if int8 else ck.fp8_part(name, axis, sl.start, sl.stop)
-        if pp is None or (not int8 and pp[1].numel() not in (1, pp[0].shape[0])):
+        if i4:
+            pp = ck.int4_part(name, axis, sl.start, sl.stop) if ck.is_int4(name) else None
+        else:
+            pp = ck.int8_part(name, axis, sl.start, sl.stop) if int8 else ck.fp8_part(name, axis, sl.start, sl.stop)
+        if pp is None or (not int8 and not i4 and pp[1].numel() not in (1, pp[0].shape[0])):
             raise ValueError("unsupported expert slice")  # a split group / 128-block scales
         return pp
 
     def build(pps, channel=True):  # row-stacked pieces of one expert -> QuantPart
+        if i4:  # from_int4 raises ValueError for a group / shape the kernel does not take
+            zs = [z for _, _, z in pps]
+            zero = None if all(z is None for z in zs) else torch.cat(
+                [z if z is not None else torch.full_like(sc, 8.0) for (_, sc, _), z in zip(pps, zs)])
+            return Q.QuantPart.from_int4(torch.cat([u for u, _, _ in pps]), torch.cat([sc for _, sc, _ in pps]),
+                                         zero, dev)
         if int8:
             zps = [z for _, _, z in pps]
             zp = None if all(z is None for z in zps) else torch.cat(

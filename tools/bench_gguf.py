@@ -65,6 +65,10 @@ def main():
     ap.add_argument("--only", nargs="*", default=None)
     ap.add_argument("--splits", type=int, nargs="*", default=None)
     ap.add_argument("--fp8", action="store_true", help="FP8 e4m3 per-channel weights of the same shapes")
+    ap.add_argument("--kind", default=None, choices=["int4", "int8", "q4_1"],
+                    help="every part of the same shapes in ONE format: int4 (group 128, asymmetric: the AWQ / "
+                         "compressed-tensors W4A16 layout), int8 (group 128) or the GGUF Q4_1 blocks (INT4's "
+                         "2,560-byte chunk, the same kernel family)")
     ap.add_argument("--prefill", action="store_true",
                     help="M > 64: the prefill GEMM from the blocks (qpf) and the M-tiled dequant-MFMA kernel vs "
                          "dequant-to-scratch + hipBLASLt vs a bf16 shadow")
@@ -86,6 +90,23 @@ def main():
                 parts.append(Q.QuantPart.from_fp8((w / sc).to(torch.float8_e4m3fn), sc, "cuda"))
                 del w
             qw = Q.QuantWeight(parts)
+        elif a.kind in ("int4", "int8"):
+            parts = []
+            for _, n, k in specs:
+                bits = 4 if a.kind == "int4" else 8
+                u = torch.randint(0, 1 << bits, (n, k), device="cuda", dtype=torch.uint8)
+                if a.kind == "int4":  # |w| ~ 0.02
+                    sc = torch.full((n, k // 128), 0.00375, device="cuda")
+                    parts.append(Q.QuantPart.from_int4(u, sc, torch.randint(0, 16, (n, k // 128), device="cuda"), "cuda"))
+                else:
+                    sc = torch.full((n, k // 128), 0.0003, device="cuda")
+                    parts.append(Q.QuantPart.from_int8(u, sc, torch.randint(-8, 8, (n, k // 128), device="cuda"), "cuda"))
+                del u
+            qw = Q.QuantWeight(parts)
+        elif a.kind == "q4_1":
+            raws = [(G.Q4_1, n, k, Q.random_blocks(rng, G.Q4_1, n, k)) for _, n, k in specs]
+            qw = Q.QuantWeight.from_raw(raws, "cuda")
+            del raws
         else:
             raws = [(t, n, k, Q.random_blocks(rng, t, n, k)) for t, n, k in specs]
             qw = Q.QuantWeight.from_raw(raws, "cuda")
@@ -143,7 +164,8 @@ def main():
                 rows.append((f"v2_S{Sx}", Sx, timed(lambda qs: Q._launch_v2(e, ws, x, qw, Sx, x16, qs))))
             del copies
             for kern, S, us in rows:
-                print(json.dumps({"proj": name, "M": M, "kernel": kern, "splits": S, "us": round(us, 2),
+                print(json.dumps({"proj": name, "fmt": a.kind or ("fp8" if a.fp8 else "q4_k_m"), "M": M, "kernel": kern,
+                                  "splits": S, "us": round(us, 2),
                                   "weight_MB": round(qw.nbytes / 1e6, 2), "cold": a.cold,
                                   "TBps": round(qw.nbytes / us / 1e6, 3),
                                   "partial_MB": round(S * M * qw.N * 4 / 1e6, 2)}), flush=True)

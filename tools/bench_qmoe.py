@@ -1,7 +1,8 @@
 """Time the quantised expert GEMM (qmoe_gemm, gguf_mfma.hip MoE mode) of one
 MoE layer (``--model``: Qwen3-30B-A3B, Mixtral-8x7B) at decode batch sizes: w13 (gathered
 token rows) and w2 (slot rows, split over K), INT8 (per-32-k scale / offset table) vs
-INT8C (per-channel, row scale in the epilogue) vs FP8 vs the GGUF block formats (q4_0,
+INT8C (per-channel, row scale in the epilogue) vs INT4 (``int4``: group 128, asymmetric,
+the AWQ / compressed-tensors W4A16 layout) vs FP8 vs the GGUF block formats (q4_0,
 q4_1, q8_0, q4_k, q5_k, q6_k: random valid blocks), at several K splits. Graph-timed over
 ``--layers`` distinct layers (their experts exceed the MALL); TB/s counts the bytes of the
 experts that received tokens (for GGUF formats: the bytes of their blocks).
@@ -37,6 +38,12 @@ def experts(E, N, K, kind, dev, g):
             raw = Q.random_blocks(np.random.default_rng(len(_blocks)), GGUF_KINDS[kind], E * N, K)
             _blocks[key] = Q.QuantMoE.from_blocks(raw, GGUF_KINDS[kind], E, N, K, dev)
         return _blocks[key].clone()
+    if kind == "int4":
+        parts = [Q.QuantPart.from_int4(torch.randint(0, 16, (N, K), device=dev, dtype=torch.uint8, generator=g),
+                                       torch.full((N, K // 128), 0.00375, device=dev),
+                                       torch.randint(0, 16, (N, K // 128), device=dev, generator=g), dev)
+                 for _ in range(E)]
+        return Q.QuantMoE(parts)
     parts = []
     for _ in range(E):
         wf = torch.randn(N, K, device=dev, generator=g) * 0.02
