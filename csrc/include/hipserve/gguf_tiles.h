@@ -21,8 +21,20 @@ namespace gq {
 // with INT8's group table: per half lane-quarter (32 k) an f16 scale s and an integer zero
 // point z in [0, 15], w = (u - z) * s (compressed-tensors: z = 8 + zero_point). The
 // nibbles sit in Q4_K's qs arrangement, so the same shifts pick them.
+// Q2_K / Q3_K: the 2-bit / 3-bit K-quants (16-element sub-blocks like Q6_K): Q2_K
+// w = d sc q - dmin m with 4-bit sc, m per sub-block; Q3_K w = d (s - 32) (q - 4) with a
+// 6-bit scale s per sub-block and the third bit of q in a separate plane (hmask).
 enum { Q4_0 = 0, Q4_1 = 1, Q8_0 = 2, Q4_K = 3, Q5_K = 4, Q6_K = 5, FP8 = 6, FP8B = 7, INT8 = 8, INT8C = 9,
-       INT4 = 10 };
+       INT4 = 10, Q2_K = 11, Q3_K = 12 };
+// Properties of a format by name, never by its place in the enum:
+// the GGUF block formats (scales inside the chunk, subnormal-integer dequant)
+constexpr bool gguf_block_format(int qt) {
+  return qt == Q4_0 || qt == Q4_1 || qt == Q8_0 || qt == Q4_K || qt == Q5_K || qt == Q6_K || qt == Q2_K || qt == Q3_K;
+}
+// the formats the block prefill GEMM (qpg_kernel) is built for
+constexpr bool qpg_format(int qt) {
+  return qt == Q4_0 || qt == Q4_1 || qt == Q8_0 || qt == Q4_K || qt == Q5_K || qt == Q6_K;
+}
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -79,9 +91,19 @@ struct Raw {
 //   INT4  [2 x 64 lanes x 16 u4 pairs][16 rows x 4 g x 2 halves x (f16 scale, f16 offset)]  2560 B
 //         byte b of lane 16 g + c: low nibble k = 64 g + b, high nibble k = 64 g + 32 + b
 //         (Q4_K's qs); table entry (c, g, h) covers k0 = 64 g + 32 h, offset = -(1024 + z)
+//   Q2_K  [64 lanes x 16 qs][16 rows x 16 scales][16 rows x (d, dmin)]          1344 B
+//   Q3_K  [64 lanes x 16 qs][16 rows x 32 hmask][16 rows x 16 int8 scales][16 rows x d]  1824 B
+//         lane 16 g + c holds bytes 16 (g & 1) .. + 15 of half g >> 1 of the row's qs: all
+//         64 of its weights in one load, step s = bit pair s >> 1 of bytes 8 (s & 1) .. + 7
+//         (kbase); its sub-block scales are bytes (g & 1) + 2 j of the 8-byte half g >> 1
+//         of the row's 16 (one uint2, as Q6_K's s2). Q3_K's 6-bit scales are unpacked to
+//         int8 s - 32 at load (4 bytes per row and super-block more than the file: the
+//         in-kernel 6-bit unpack is the VALU cost that bounds this kernel family); its
+//         hmask bytes 16 (g & 1) .. + 15 hold the third bit of step s at bit 4 (g >> 1) + (s >> 1)
 template <int QT>
 constexpr int chunk_bytes() {
-  return QT == Q4_K ? 2304 : QT == Q5_K ? 2816 : QT == Q6_K ? 3360 : QT == Q8_0 ? 4352 : QT == Q4_0 ? 2304
+  return QT == Q2_K ? 1344 : QT == Q3_K ? 1824
+       : QT == Q4_K ? 2304 : QT == Q5_K ? 2816 : QT == Q6_K ? 3360 : QT == Q8_0 ? 4352 : QT == Q4_0 ? 2304
        : QT == Q4_1 || QT == INT4 ? 2560 : QT == FP8 || QT == INT8C ? 4096 : QT == FP8B ? 4224 : 4608;
 }
 // formats whose per-row scale (Part::rs) multiplies the accumulators in the epilogue
@@ -137,6 +159,20 @@ HS_DEVICE void load_raw(const unsigned char* ch, int g, int c, int lane, Raw& r)
     r.s2[0] = sc.x;
     r.s2[1] = sc.y;
     r.h[0] = *reinterpret_cast<const unsigned short*>(ch + 3328 + 2 * c);
+  } else if constexpr (QT == Q2_K || QT == Q3_K) {
+    r.v[0] = ld16(ch + 16 * lane);
+    constexpr int so = QT == Q2_K ? 1024 : 1536;  // the row's 16 sub-block scales
+    if constexpr (QT == Q3_K) r.v[1] = ld16(ch + 1024 + 32 * c + 16 * (g & 1));
+    const uint2 sc = *reinterpret_cast<const uint2*>(ch + so + 16 * c + 8 * (g >> 1));  // sub-blocks 8h..8h+7
+    r.s2[0] = sc.x;
+    r.s2[1] = sc.y;
+    if constexpr (QT == Q2_K) {
+      const unsigned dd = *reinterpret_cast<const unsigned*>(ch + 1280 + 4 * c);  // d, dmin
+      r.h[0] = dd & 0xFFFF;
+      r.h[1] = dd >> 16;
+    } else {
+      r.h[0] = *reinterpret_cast<const unsigned short*>(ch + 1792 + 2 * c);
+    }
   } else if constexpr (QT == INT8) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) r.v[i] = ld16(ch + 1024 * i + 16 * lane);
@@ -195,6 +231,8 @@ HS_DEVICE int kbase(int g, int s) {
   if constexpr (QT == Q6_K) {
     const int q = (g & 1) + 2 * (s >> 2);
     return 128 * (g >> 1) + 32 * q + 8 * (s & 3);
+  } else if constexpr (QT == Q2_K || QT == Q3_K) {
+    return 128 * (g >> 1) + 32 * (s >> 1) + 16 * (g & 1) + 8 * (s & 1);
   } else {
     return 64 * g + 32 * (s >> 2) + 8 * (s & 3);
   }
@@ -213,16 +251,33 @@ HS_DEVICE int kbase(int g, int s) {
 // test_mfma_v2_tiny_scales). Range: d 2^(24-kSub) must stay below 65504 —
 // ops/quant.py sub_scale_ok() checks every block's scale at load (Q4_K / Q4_0 / Q4_1
 // d sc < 0.25, Q5_K < 0.125, Q6_K < 0.0625, Q8_0 < 0.0156) and sends weights beyond
-// it to the v1 kernel.
+// it to the v1 kernel. Q2_K (q < 4) takes the highest shift that keeps q << kSub below
+// 1024, 8: d sc < 65504 / 2^16 ~ 0.9995; Q3_K (q < 8) 7: |d (s - 32)| < 65504 / 2^17 ~ 0.4998.
+// These two have no v1 kernel: a weight beyond the range is held as bf16 (QuantWeight.from_gguf).
 template <int QT>
-constexpr int sub_shift() { return QT == Q5_K ? 5 : QT == Q6_K ? 4 : QT == Q8_0 ? 2 : 6; }
+constexpr int sub_shift() { return QT == Q2_K ? 8 : QT == Q3_K ? 7 : QT == Q5_K ? 5 : QT == Q6_K ? 4 : QT == Q8_0 ? 2 : 6; }
 template <int QT>
 constexpr float sub_up() {
-  return QT == Q4_K || QT == Q5_K || QT == Q6_K || QT == Q8_0 || QT == Q4_0 || QT == Q4_1
-             ? (float)(1 << (24 - sub_shift<QT>())) : 1.f;
+  return gguf_block_format(QT) ? (float)(1 << (24 - sub_shift<QT>())) : 1.f;
 }
 template <int QT>
-constexpr float sub_zero() { return QT == Q4_0 ? -8.f : QT == Q6_K ? -32.f : QT == Q8_0 ? -128.f : 0.f; }
+constexpr float sub_zero() { return QT == Q4_0 ? -8.f : QT == Q6_K ? -32.f : QT == Q8_0 ? -128.f : QT == Q3_K ? -4.f : 0.f; }
+
+// Q2_K / Q3_K: 2-bit fields at bit 2 j of bytes (0, 2) / (1, 3) of w moved to bit S of each half
+template <int S>
+HS_DEVICE void bit2_pairs(unsigned w, int j, unsigned& p02, unsigned& p13) {
+  constexpr unsigned m = 0x00030003u << S;
+  p02 = (2 * j <= S ? w << (S - 2 * j) : w >> (2 * j - S)) & m;
+  p13 = (2 * j + 8 >= S ? w >> (2 * j + 8 - S) : w << (S - 2 * j - 8)) & m;
+}
+// Q3_K: bit j of bytes (0, 2) / (1, 3) of hm (the hmask word already shifted down by
+// 4 (g >> 1)) ORed in at bit S + 2 of each half
+template <int S>
+HS_DEVICE void hbit_pairs(unsigned hm, int j, unsigned& p02, unsigned& p13) {
+  constexpr unsigned m = 0x00010001u << (S + 2);
+  p02 |= (j <= S + 2 ? hm << (S + 2 - j) : hm >> (j - S - 2)) & m;
+  p13 |= (j + 8 >= S + 2 ? hm >> (j + 8 - S - 2) : hm << (S + 2 - j - 8)) & m;
+}
 
 // Decode step s (8 weights) of the lane's super-chunk. ints(): the 8 quantised
 // integers (minus the format's zero point) as exact f16, pair order; step(): the
@@ -232,7 +287,9 @@ template <int QT>
 struct Dec {
   h2 dA, cA, dB, cB;        // per-step-group scale / offset pairs (K-quants: sub-blocks; SoA: blocks)
   float fdA, fcA, fdB, fcB;  // the same in fp32
-  float d6;                  // Q6_K super-block scale
+  float d6;                  // Q6_K / Q2_K / Q3_K super-block scale
+  float m6;                  // Q2_K: -dmin
+  u32x4 hm;                  // Q3_K: the lane's hmask bytes >> 4 (g >> 1): bit j of a byte = step pair j
 
   HS_DEVICE void setup(const Raw& r, int g) {
     fcA = fcB = 0.f;
@@ -248,6 +305,14 @@ struct Dec {
       fcB = -dmin * m2;
     } else if constexpr (QT == Q6_K) {
       d6 = h2f(r.h[0]);
+    } else if constexpr (QT == Q2_K) {
+      d6 = h2f(r.h[0]);
+      m6 = -h2f(r.h[1]);
+    } else if constexpr (QT == Q3_K) {
+      d6 = h2f(r.h[0]);
+      const int hs = 4 * (g >> 1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) hm[i] = r.v[1][i] >> hs;  // bits of the byte above leak in: masked on use
     } else if constexpr (QT == FP8 || QT == FP8B || QT == INT8C) {
       fdA = fdB = QT == FP8B ? __builtin_bit_cast(float, r.s2[0]) : 1.f;
     } else if constexpr (QT == INT8 || QT == INT4) {  // c = offset (-1024 - 128 - zp / -1024 - z), applied before the scale
@@ -284,6 +349,16 @@ struct Dec {
       // of the lane's scale word (s >> 2)
       d = d6 * (float)(signed char)((r.s2[s >> 2] >> (8 * (2 * (g & 1) + ((s & 3) >> 1)))) & 0xFF);
       c = 0.f;
+    } else if constexpr (QT == Q2_K || QT == Q3_K) {
+      // sub-block 8h + 2j + (g & 1), j = s >> 1: byte 2 (j & 1) + (g & 1) of the lane's scale word j >> 1
+      const unsigned b = (r.s2[s >> 2] >> (8 * (2 * ((s >> 1) & 1) + (g & 1)))) & 0xFF;
+      if constexpr (QT == Q2_K) {
+        d = d6 * (float)(b & 0xF);
+        c = m6 * (float)(b >> 4);
+      } else {
+        d = d6 * (float)(signed char)b;
+        c = 0.f;
+      }
     } else if constexpr (QT == INT8 || QT == INT4) {
       d = s < 4 ? fdA : fdB;
       c = 0.f;
@@ -366,6 +441,18 @@ struct Dec {
       p[2] |= (hb & 0x00030003u) << 4;
       p[3] |= ((hb >> 8) & 0x00030003u) << 4;
       z = (_Float16)1056.f;  // q6 - 32
+    } else if constexpr (QT == Q2_K || QT == Q3_K) {
+      const int j = s >> 1;
+      const unsigned wa = r.v[0][2 * (s & 1)], wb = r.v[0][2 * (s & 1) + 1];
+      bit2_pairs<0>(wa, j, p[0], p[1]);
+      bit2_pairs<0>(wb, j, p[2], p[3]);
+      if constexpr (QT == Q3_K) {
+        hbit_pairs<0>(hm[2 * (s & 1)], j, p[0], p[1]);
+        hbit_pairs<0>(hm[2 * (s & 1) + 1], j, p[2], p[3]);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) p[i] |= kMagic;
+      z = (_Float16)(QT == Q3_K ? 1028.f : 1024.f);  // q3 - 4 / q2
     } else if constexpr (QT == Q8_0) {
       const u32x4 qv[4] = {r.v[0], r.v[1], r.v[2], r.v[3]};
       const unsigned wa = qv[s >> 1][2 * (s & 1)] ^ 0x80808080u, wb = qv[s >> 1][2 * (s & 1) + 1] ^ 0x80808080u;
@@ -435,6 +522,15 @@ struct Dec {
       p[1] = ((la >> (sh + 8 - S)) & m) | (((ha >> 8) & 0x00030003u) << (4 + S));
       p[2] = ((sh <= S ? lb << (S - sh) : lb >> (sh - S)) & m) | ((hb & 0x00030003u) << (4 + S));
       p[3] = ((lb >> (sh + 8 - S)) & m) | (((hb >> 8) & 0x00030003u) << (4 + S));
+    } else if constexpr (QT == Q2_K || QT == Q3_K) {
+      const int j = s >> 1;
+      const unsigned wa = r.v[0][2 * (s & 1)], wb = r.v[0][2 * (s & 1) + 1];
+      bit2_pairs<S>(wa, j, p[0], p[1]);
+      bit2_pairs<S>(wb, j, p[2], p[3]);
+      if constexpr (QT == Q3_K) {
+        hbit_pairs<S>(hm[2 * (s & 1)], j, p[0], p[1]);
+        hbit_pairs<S>(hm[2 * (s & 1) + 1], j, p[2], p[3]);
+      }
     } else {  // Q8_0: int8 + 128 in [0, 255]
       const u32x4 qv[4] = {r.v[0], r.v[1], r.v[2], r.v[3]};
       const unsigned wa = qv[s >> 1][2 * (s & 1)] ^ 0x80808080u, wb = qv[s >> 1][2 * (s & 1) + 1] ^ 0x80808080u;
@@ -448,14 +544,19 @@ struct Dec {
   }
 
   HS_DEVICE f16x8 step(const Raw& r, int g, int s) const {
-    if constexpr (QT == Q4_K || QT == Q5_K || QT == Q6_K || QT == Q8_0 || QT == Q4_0 || QT == Q4_1) {
+    if constexpr (gguf_block_format(QT)) {
       const u32x4 qu = __builtin_bit_cast(u32x4, sub_ints(r, g, s));
       h2 dd, cc;
-      if constexpr (QT == Q6_K) {
+      if constexpr (QT == Q6_K || QT == Q3_K) {
         float d, c;
         scale(r, g, s, d, c);
         dd = splat(d * sub_up<QT>());
         cc = splat(sub_zero<QT>() * (float)(_Float16)d);
+      } else if constexpr (QT == Q2_K) {  // Q4_K's form with a scale / min pair per two steps
+        float d, c;
+        scale(r, g, s, d, c);
+        dd = splat(d * sub_up<QT>());
+        cc = splat(c);
       } else if constexpr (QT == Q4_0 || QT == Q4_1) {
         dd = (s >> 2) ? dB : dA;
         cc = (s >> 2) ? cB : cA;

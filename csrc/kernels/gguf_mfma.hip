@@ -393,9 +393,11 @@ void launch_t(void* out, long out_stride, float* ws, const void* x, long x_strid
 // scratch per lane), while Q4_0 / Q4_1 / Q4_K reach 4 waves unforced — so the GGUF formats
 // stay unconstrained (profiles/r7_gguf_moe_resources.md: every instantiation, scratch 0)
 // INT4 carries INT8's table with Q4_1's bytes: unconstrained like both (profiles/int4_resources.md)
+// Q2_K / Q3_K are GGUF blocks with a per-step scale like Q6_K: unconstrained too
+// (profiles/q2k_q3k_resources.md)
 template <int QT, int MT>
 constexpr int qmoe_waves() {
-  return QT <= Q6_K || QT == INT8 || QT == INT4 ? 1 : MT == 1 ? 4 : 1;
+  return gguf_block_format(QT) || QT == INT8 || QT == INT4 ? 1 : MT == 1 ? 4 : 1;
 }
 template <int QT, int MT, int RT, int NWAVES>
 __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(qmoe_waves<QT, MT>())))
@@ -836,6 +838,8 @@ int gguf_tiled_chunk_bytes(int qtype) {
     case INT8: return chunk_bytes<INT8>();
     case INT8C: return chunk_bytes<INT8C>();
     case INT4: return chunk_bytes<INT4>();
+    case Q2_K: return chunk_bytes<Q2_K>();
+    case Q3_K: return chunk_bytes<Q3_K>();
   }
   return 0;
 }
@@ -889,6 +893,8 @@ void launch_gguf_gemm_parts(void* out, long out_stride, float* ws, const void* x
       case INT8: launch_t<INT8, INT8>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
       case INT8C: launch_t<INT8C, INT8C>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
       case INT4: launch_t<INT4, INT4>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
+      case Q2_K: launch_t<Q2_K, Q2_K>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
+      case Q3_K: launch_t<Q3_K, Q3_K>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
     }
   }
 }
@@ -912,6 +918,8 @@ bool launch_qmoe_gemm(void* out, long out_stride, float* ws, const void* x, long
     case INT8: moe_launch_t<INT8>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
     case INT8C: moe_launch_t<INT8C>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
     case INT4: moe_launch_t<INT4>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
+    case Q2_K: moe_launch_t<Q2_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
+    case Q3_K: moe_launch_t<Q3_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
   }
   return false;
 }
@@ -919,7 +927,7 @@ bool launch_qmoe_gemm(void* out, long out_stride, float* ws, const void* x, long
 // Prefill GEMM over tiled GGUF parts (qpg_kernel) on x16 / rsc from launch_x_f16_pairs
 // (row stride K). STORE: out[:, col .. col + rows) per
 // part; ADD: out is the residual (updated in place); GLU / GEGLU: parts 0 / 1 are gate / up
-// (same format and rows), out[M, rows] = act(gate) * up. Formats: GGUF (Q4_0 .. Q6_K);
+// (same format and rows), out[M, rows] = act(gate) * up. Formats: qpg_format() (Q4_0 .. Q6_K; not Q2_K / Q3_K);
 // a mix of formats launches once per format (one body per launch: a two-format kernel
 // spills). Returns false for shapes / formats it does not take (the caller falls back).
 void launch_x_f16_pairs(void* x16, float* rsc, const void* x, long ldx, int M, int K, hipStream_t s) {
@@ -936,7 +944,7 @@ bool launch_gguf_prefill(int epi, void* out, long ldo, const void* x16, const fl
   // 32-bit buffer offsets inside one x tile
   if ((long)256 * ldx * 2 >= (1L << 31)) return false;  // the largest tile's x rows (qpg: 256)
   for (int i = 0; i < nparts; ++i)
-    if (parts[i].qtype < Q4_0 || parts[i].qtype > Q6_K || parts[i].rows % 16) return false;
+    if (!qpg_format(parts[i].qtype) || parts[i].rows % 16) return false;  // Q2_K / Q3_K: no block prefill body
   if (glu && (parts[0].qtype != parts[1].qtype || parts[0].rows != parts[1].rows)) return false;
   int fmts[kMaxParts], nf = 0;
   for (int i = 0; i < nparts; ++i) {
@@ -1000,6 +1008,8 @@ void launch_gguf_dequant_tiled(void* out, const void* q, const float* rs, int qt
     case INT8: dequant_tiled_kernel<INT8><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
     case INT8C: dequant_tiled_kernel<INT8C><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
     case INT4: dequant_tiled_kernel<INT4><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
+    case Q2_K: dequant_tiled_kernel<Q2_K><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
+    case Q3_K: dequant_tiled_kernel<Q3_K><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
   }
 }
 

@@ -331,7 +331,7 @@ int64_t gguf_gemm_parts(at::Tensor& out, at::Tensor& ws, const at::Tensor& x, co
   const int S = (nsb + per - 1) / per;
   hipserve::GgufPart P[4];
   for (int i = 0; i < np; ++i) {
-    TORCH_CHECK(qtypes[i] >= 0 && qtypes[i] <= 10, "gguf_gemm_parts: kernel qtype 0-10");
+    TORCH_CHECK(qtypes[i] >= 0 && qtypes[i] <= 12, "gguf_gemm_parts: kernel qtype 0-12");
     const bool fp8 = row_scaled_qt(qtypes[i]);
     TORCH_CHECK(!fp8 || (rss[i].scalar_type() == at::kFloat && rss[i].is_contiguous() && rss[i].numel() == rows[i] &&
                          rss[i].device() == x.device()), "FP8 / INT8C parts need an fp32 row scale per row");
@@ -406,7 +406,7 @@ bool gguf_prefill(at::Tensor& out, const at::Tensor& x16, const at::Tensor& rsc,
   for (int i = 0; i < np; ++i) {
     TORCH_CHECK(qs[i].scalar_type() == at::kByte && qs[i].is_contiguous() && qs[i].device() == x16.device());
     TORCH_CHECK(rows[i] % 16 == 0 && rows[i] > 0 && cols[i] % 4 == 0, "gguf_prefill: 16-row parts, 4-aligned columns");
-    TORCH_CHECK(qtypes[i] >= 0 && qtypes[i] <= 8 &&
+    TORCH_CHECK(qtypes[i] >= 0 && qtypes[i] <= 12 &&  // formats without a prefill body: the launcher returns false
                     qs[i].numel() == rows[i] / 16 * nsb * hipserve::gguf_tiled_chunk_bytes(qtypes[i]),
                 "gguf_prefill: part q is not a tiled [N/16, K/256, chunk] tensor of its format");
     P[i] = hipserve::GgufPart{qs[i].data_ptr(), nullptr, (int)qtypes[i], (int)rows[i], (int)cols[i]};
@@ -423,10 +423,10 @@ int64_t qmoe_gemm(at::Tensor& out, at::Tensor& ws, const at::Tensor& x, const at
                   int64_t qtype, int64_t N, int64_t K, const at::Tensor& slots, const at::Tensor& tile_expert,
                   int64_t tile, int64_t gather_k, int64_t splits, bool kmajor, int64_t glu) {
   CHECK_DEV(x); CHECK_BF16(x); CHECK_ROWMAJOR(x);
-  // 0-5: GGUF blocks Q4_0, Q4_1, Q8_0, Q4_K, Q5_K, Q6_K (scales inside the blocks, no rs)
-  TORCH_CHECK((qtype >= 0 && qtype <= 6) || (qtype >= 8 && qtype <= 10),
-              "qmoe_gemm: expert formats GGUF Q4_0 / Q4_1 / Q8_0 / Q4_K / Q5_K / Q6_K, FP8 (per-row scale), INT8, INT8C, "
-              "INT4");
+  // 0-5, 11, 12: GGUF blocks Q4_0, Q4_1, Q8_0, Q4_K, Q5_K, Q6_K, Q2_K, Q3_K (scales inside the blocks, no rs)
+  TORCH_CHECK((qtype >= 0 && qtype <= 6) || (qtype >= 8 && qtype <= 12),
+              "qmoe_gemm: expert formats GGUF Q4_0 / Q4_1 / Q8_0 / Q4_K / Q5_K / Q6_K / Q2_K / Q3_K, FP8 (per-row scale), "
+              "INT8, INT8C, INT4");
   TORCH_CHECK(tile == 16 || tile == 32 || tile == 64, "qmoe_gemm: tile 16/32/64");
   TORCH_CHECK(N % 16 == 0 && K % 256 == 0 && x.size(1) >= K && x.stride(0) % 8 == 0, "qmoe_gemm: shapes");
   TORCH_CHECK(slots.scalar_type() == at::kInt && tile_expert.scalar_type() == at::kInt && slots.is_contiguous() &&
@@ -479,7 +479,7 @@ void gguf_dequant_tiled(at::Tensor& out, const at::Tensor& q, const at::Tensor& 
                 "gguf_dequant_tiled: packed matrices of nrows rows (glu: nrows % 128 == 0)");
     TORCH_CHECK(out.numel() >= N / nrows * ((nrows + 127) / 128 * 128) * K, "gguf_dequant_tiled: packed out size");
   }
-  TORCH_CHECK(qtype >= 0 && qtype <= 10 && q.scalar_type() == at::kByte && q.is_contiguous());
+  TORCH_CHECK(qtype >= 0 && qtype <= 12 && q.scalar_type() == at::kByte && q.is_contiguous());
   TORCH_CHECK(q.numel() == N / 16 * (K / 256) * hipserve::gguf_tiled_chunk_bytes(qtype), "not a tiled tensor");
   TORCH_CHECK(!kmajor || nrows <= 0 || (nrows % 16 == 0 && N % nrows == 0), "gguf_dequant_tiled: k-major matrices of nrows rows");
   const bool fp8 = row_scaled_qt(qtype);

@@ -445,7 +445,7 @@ def _hf_cache_dir(repo_id: str) -> str | None:
     return max(snaps, key=lambda p: (os.path.getmtime(p), p)) if snaps else None
 
 
-GGUF_QUANTS = ("q4_k_m", "q8_0", "q4_0")
+GGUF_QUANTS = ("q4_k_m", "q8_0", "q4_0", "q3_k_m", "q2_k")
 
 
 def default_batched_tokens(model: str, load_format: str = "auto", quantization: str | None = None) -> int:

@@ -285,6 +285,11 @@ class LlamaModel(MoEMixin):
                                 "down_exps")},
         "q4_0": {**{n: 2 for n in ("q", "k", "v", "o", "gate", "up", "down", "gate_exps", "up_exps", "down_exps")},
                  "output": 14},
+        # approximations of llama.cpp's Q3_K_M / Q2_K mixes (10 = Q2_K, 11 = Q3_K)
+        "q3_k_m": {"q": 11, "k": 11, "v": 12, "o": 12, "gate": 11, "up": 11, "down": 12, "output": 14,
+                   "gate_exps": 11, "up_exps": 11, "down_exps": 12},
+        "q2_k": {"q": 10, "k": 10, "v": 11, "o": 11, "gate": 10, "up": 10, "down": 11, "output": 14,
+                 "gate_exps": 10, "up_exps": 10, "down_exps": 11},
     }
     # distinct random expert stacks generated on the host per (format, shape); further layers
     # reuse them round-robin (each layer still holds its own device copy)
@@ -318,12 +323,12 @@ class LlamaModel(MoEMixin):
         nq, nkv, V = cfg.num_heads, cfg.num_kv_heads, cfg.vocab_size
         rng = np.random.default_rng(seed)
 
-        def qtype(kind, k):  # llama.cpp-style fallback when K is not a multiple of the super-block
-            t = types[kind]
-            return t if k % G.BLOCK[t][0] == 0 else G.Q8_0
+        def qtype(kind, k, n=16):  # llama.cpp-style fallback when K is not a multiple of the super-block
+            t = types[kind]     # (Q2_K / Q3_K: tiled layout only, so also when N is no multiple of 16)
+            return t if k % G.BLOCK[t][0] == 0 and not (t in (G.Q2_K, G.Q3_K) and n % 16) else G.Q8_0
 
         def mat(*specs):  # (kind, N, K) parts stacked along N
-            raws = [(qtype(k, kk), n, kk, Q.random_blocks(rng, qtype(k, kk), n, kk)) for k, n, kk in specs]
+            raws = [(qtype(k, kk, n), n, kk, Q.random_blocks(rng, qtype(k, kk, n), n, kk)) for k, n, kk in specs]
             if dev.type == "cuda":
                 return Q.QuantWeight.from_raw(raws, dev)
             return torch.cat([torch.from_numpy(G.dequantize(r, t, n * kk).reshape(n, kk)).to(dt)

@@ -37,7 +37,7 @@ INT8C = 1003
 # w = (u - z) * s (gguf_tiles.h INT4)
 INT4 = 1004
 KERNEL_QT = {G.Q4_0: 0, G.Q4_1: 1, G.Q8_0: 2, G.Q4_K: 3, G.Q5_K: 4, G.Q6_K: 5, FP8: 6, FP8B: 7, INT8: 8,
-             INT8C: 9, INT4: 10}
+             INT8C: 9, INT4: 10, G.Q2_K: 11, G.Q3_K: 12}
 MAX_FUSED_M = 64
 # the W8A8 FP8 decode GEMM (fp8_decode.hip) also takes the decode graph buckets above 64
 # rows (up to 256, max_num_seqs' default): one weight stream per step instead of the
@@ -82,7 +82,7 @@ def repack(raw: np.ndarray, qtype: int, N: int, K: int):
 
 
 CHUNK_BYTES = {G.Q4_K: 2304, G.Q5_K: 2816, G.Q6_K: 3360, G.Q8_0: 4352, G.Q4_0: 2304, G.Q4_1: 2560,
-               FP8: 4096, FP8B: 4224, INT8: 4608, INT8C: 4096, INT4: 2560}
+               FP8: 4096, FP8B: 4224, INT8: 4608, INT8C: 4096, INT4: 2560, G.Q2_K: 1344, G.Q3_K: 1824}
 
 
 def _lanes(a: np.ndarray, n_ld: int) -> np.ndarray:
@@ -110,6 +110,15 @@ def repack_tiled(raw: np.ndarray, qtype: int, N: int, K: int) -> np.ndarray:
         parts = [_lanes(b[..., 0:128].reshape(R, nsb, 16, 4, 2, 16), 2),
                  b[..., 128:192].reshape(R, nsb, 1024), b[..., 192:208].reshape(R, nsb, 256),
                  b[..., 208:210].reshape(R, nsb, 32)]
+    elif qtype == G.Q2_K:
+        # lane 16 g + c: bytes 16 g .. + 15 of the row's qs (half g >> 1, bytes 16 (g & 1) .. + 15 of it)
+        parts = [_lanes(b[..., 16:80].reshape(R, nsb, 16, 4, 1, 16), 1), b[..., 0:16].reshape(R, nsb, 256),
+                 b[..., 80:84].reshape(R, nsb, 64)]
+    elif qtype == G.Q3_K:
+        # the 6-bit scales unpacked here to int8 s - 32, not in the kernel (4 bytes per row and super-block)
+        sc = G.q3k_scales(b[..., 96:108].reshape(-1, 12)).view(np.uint8)
+        parts = [_lanes(b[..., 32:96].reshape(R, nsb, 16, 4, 1, 16), 1), b[..., 0:32].reshape(R, nsb, 512),
+                 sc.reshape(R, nsb, 256), b[..., 108:110].reshape(R, nsb, 32)]
     else:
         blk = b.reshape(R, nsb, 16, per, bb)
         if qtype == G.Q8_0:
@@ -129,8 +138,9 @@ def repack_tiled(raw: np.ndarray, qtype: int, N: int, K: int) -> np.ndarray:
 # gguf_mfma.hip places each quantised integer at bit SUB_SHIFT of a subnormal f16 and
 # scales it by 2^(24 - SUB_SHIFT) inside the f16 FMA: every block scale must stay below
 # 65504 / 2^(24 - SUB_SHIFT) (|w| up to ~2-4). Weights beyond that (none in practice)
-# run on the v1 kernel.
-SUB_SHIFT = {G.Q4_K: 6, G.Q5_K: 5, G.Q6_K: 4, G.Q8_0: 2, G.Q4_0: 6, G.Q4_1: 6}
+# run on the v1 kernel. Q2_K / Q3_K (2- / 3-bit integers: shifts 8 / 7, limits 0.9995 / 0.4998) have
+# no v1 kernel: QuantWeight.from_gguf keeps such a weight as bf16.
+SUB_SHIFT = {G.Q4_K: 6, G.Q5_K: 5, G.Q6_K: 4, G.Q8_0: 2, G.Q4_0: 6, G.Q4_1: 6, G.Q2_K: 8, G.Q3_K: 7}
 
 
 def sub_scale_ok(raw, qtype: int) -> bool:
@@ -147,6 +157,12 @@ def sub_scale_ok(raw, qtype: int) -> bool:
         prod = f16(b[:, 0:2])[:, None] * sc
     elif qtype == G.Q6_K:
         prod = f16(b[:, 208:210])[:, None] * np.abs(np.ascontiguousarray(b[:, 192:208]).view(np.int8).astype(np.float32))
+    elif qtype == G.Q2_K:
+        prod = f16(b[:, 80:82])[:, None] * (b[:, 0:16] & 0xF).astype(np.float32)
+        if prod.size and not np.max(f16(b[:, 82:84])[:, None] * (b[:, 0:16] >> 4).astype(np.float32)) < 65504.0:
+            return False  # dmin m is the f16 FMA's addend
+    elif qtype == G.Q3_K:
+        prod = f16(b[:, 108:110])[:, None] * np.abs(G.q3k_scales(b[:, 96:108]).astype(np.float32))
     else:
         prod = f16(b[:, 0:2])[:, None]
     # (no lower bound: a d * sc below the f16 normal range is kept with MORE mantissa
@@ -328,8 +344,15 @@ class QuantWeight:
         return sum(p.nbytes for p in self.parts)
 
     @staticmethod
-    def supported(qtype: int, K: int) -> bool:
-        return qtype in KERNEL_QT and K % 256 == 0
+    def supported(qtype: int, K: int, N: int | None = None, raw=None) -> bool:
+        """A GGUF tensor of ``qtype`` stays quantised. Q2_K / Q3_K exist in the tiled
+        (v2) layout only: with ``N`` / ``raw`` also N % 16 == 0 and every block scale
+        inside the subnormal-dequant range."""
+        if qtype not in KERNEL_QT or K % 256:
+            return False
+        if qtype in (G.Q2_K, G.Q3_K):
+            return (N is None or N % 16 == 0) and (raw is None or sub_scale_ok(raw, qtype))
+        return True
 
     @classmethod
     def from_gguf(cls, gf: "G.GGUFFile", names, device):
@@ -337,7 +360,7 @@ class QuantWeight:
         for n in names:
             t = gf.tensors[n]
             N, K = t.rows_cols
-            if not cls.supported(t.type, K):
+            if not cls.supported(t.type, K, N, gf.raw(n) if t.type in (G.Q2_K, G.Q3_K) else None):
                 return torch.cat([torch.from_numpy(gf.tensor_f32(x)).to(device, torch.bfloat16)
                                   for x in names], 0)
             parts.append(QuantPart.build(gf.raw(n), t.type, N, K, device))
@@ -362,7 +385,7 @@ class QuantWeight:
 
 # synthetic block scales: |w| ~ 0.02 for every format (random-init benchmarks)
 _SYNTH_D = {G.Q4_K: (8e-5, 6e-4), G.Q5_K: (4e-5, 6e-4), G.Q6_K: (1.5e-5, 0.0), G.Q8_0: (2.5e-4, 0.0),
-            G.Q4_0: (4e-3, 0.0), G.Q4_1: (4e-3, -0.03)}
+            G.Q4_0: (4e-3, 0.0), G.Q4_1: (4e-3, -0.03), G.Q2_K: (1.8e-3, 2.7e-3), G.Q3_K: (6.25e-4, 0.0)}
 
 
 def random_blocks(rng: np.random.Generator, qtype: int, N: int, K: int) -> np.ndarray:
@@ -379,6 +402,11 @@ def random_blocks(rng: np.random.Generator, qtype: int, N: int, K: int) -> np.nd
         b[:, :, 2:4] = f16(dm)
     elif qtype == G.Q6_K:
         b[:, :, 208:210] = f16(d)
+    elif qtype == G.Q2_K:
+        b[:, :, 80:82] = f16(d)
+        b[:, :, 82:84] = f16(dm)
+    elif qtype == G.Q3_K:
+        b[:, :, 108:110] = f16(d)
     elif qtype in (G.Q8_0, G.Q4_0, G.Q5_0):
         b[:, :, 0:2] = f16(d)
     elif qtype in (G.Q4_1, G.Q5_1):
@@ -683,7 +711,10 @@ def quant_partial(x: torch.Tensor, w: QuantWeight, x16: torch.Tensor | None = No
 QPREFILL_MODE = os.environ.get("HIPSERVE_QPREFILL", "auto")
 QPREFILL = QPREFILL_MODE != "0"
 QPF_CHOICE: dict = {}  # weight signature -> the block kernel was faster at start-up
-GGUF_KQT = (0, 1, 2, 3, 4, 5)  # kernel qtypes Q4_0 .. Q6_K
+QPG_KQT = (0, 1, 2, 3, 4, 5)  # kernel qtypes Q4_0 .. Q6_K: the block prefill GEMM (qpg_kernel) takes them
+# every GGUF block format (+ Q2_K, Q3_K): no resident bf16 shadow by default, expert stacks
+# checked against the subnormal-dequant range
+GGUF_KQT = QPG_KQT + (KERNEL_QT[G.Q2_K], KERNEL_QT[G.Q3_K])
 
 
 def qprefill_ok(w, M: int, glu: bool = False, timed: bool = True) -> bool:
@@ -693,7 +724,7 @@ def qprefill_ok(w, M: int, glu: bool = False, timed: bool = True) -> bool:
     ``timed``: and the start-up timing (``auto``) did not prefer dequant + hipBLASLt."""
     if not (QPREFILL and isinstance(w, QuantWeight) and M > MAX_FUSED_M and w.dense is None):
         return False
-    if not (w.v2 and w.parts[0].q.is_cuda and all(p.kqt in GGUF_KQT for p in w.parts)
+    if not (w.v2 and w.parts[0].q.is_cuda and all(p.kqt in QPG_KQT for p in w.parts)
             and hasattr(torch.ops.hipserve, "gguf_prefill")):
         return False
     if glu:
@@ -922,11 +953,11 @@ class QuantMoE:
     for the formats whose scales sit inside the chunks). Formats: INT8 (compressed-tensors
     8-bit, the reference's AWQ-8bit export), INT4 (AutoAWQ gemm / compressed-tensors 4-bit),
     per-channel FP8, and the GGUF blocks Q4_0 /
-    Q4_1 / Q8_0 / Q4_K / Q5_K / Q6_K (``from_blocks``: a MoE GGUF's ``*_exps`` tensors stay
+    Q4_1 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K (``from_blocks``: a MoE GGUF's ``*_exps`` tensors stay
     resident as their blocks only). Prefill runs bf16 expert GEMMs on ``dense`` (a resident
     shadow when asked for, else a per-call dequantised scratch)."""
 
-    # GGUF Q4_0 .. Q6_K (scales in the blocks), FP8 (per-row scale), INT8, INT8C (per-row scale), INT4
+    # GGUF Q4_0 .. Q6_K, Q2_K, Q3_K (scales in the blocks), FP8 (per-row scale), INT8, INT8C (per-row scale), INT4
     KERNEL_QTS = GGUF_KQT + (6, 8, 9, 10)
 
     def __init__(self, parts: list, kmajor: bool = False):

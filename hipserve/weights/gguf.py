@@ -10,7 +10,7 @@ Python package is available):
   tensor infos (GGUF v2/v3), ``model_config()`` from ``llama.*`` metadata;
 * block codecs    — numpy reference dequantisers (and quantisers, used to write
   synthetic test/benchmark files) for F32/F16/BF16/Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/
-  Q4_K/Q5_K/Q6_K, bit-exact with ggml's block layouts;
+  Q2_K/Q3_K/Q4_K/Q5_K/Q6_K, bit-exact with ggml's block layouts;
 * ``GGUFTokenizer`` — SentencePiece-BPE (``llama``) and byte-level BPE (``gpt2``,
   Llama-3) tokenizers built from the embedded vocab;
 * ``load_gguf_weights`` — maps ``blk.N.*`` tensors onto the hipserve model; the
@@ -41,7 +41,8 @@ TYPE_NAMES = {F32: "F32", F16: "F16", Q4_0: "Q4_0", Q4_1: "Q4_1", Q5_0: "Q5_0", 
               Q6_K: "Q6_K", Q8_K: "Q8_K", BF16: "BF16"}
 # (block elements, bytes per block)
 BLOCK = {F32: (1, 4), F16: (1, 2), BF16: (1, 2), Q4_0: (32, 18), Q4_1: (32, 20), Q5_0: (32, 22),
-         Q5_1: (32, 24), Q8_0: (32, 34), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210)}
+         Q5_1: (32, 24), Q8_0: (32, 34), Q2_K: (256, 84), Q3_K: (256, 110), Q4_K: (256, 144),
+         Q5_K: (256, 176), Q6_K: (256, 210)}
 
 # metadata value types
 _U8, _I8, _U16, _I16, _U32, _I32, _F32, _BOOL, _STR, _ARR, _U64, _I64, _F64 = range(13)
@@ -219,6 +220,23 @@ def _scale_min_k4(scales: np.ndarray):
     return sc.astype(np.float32), mn.astype(np.float32)
 
 
+def q3k_scales(scales: np.ndarray) -> np.ndarray:
+    """[nb, 12] packed Q3_K scales -> the 16 signed sub-block scales s - 32, int8 [nb, 16]:
+    low 4 bits in the nibbles of bytes 0-7, high 2 bits in bytes 8-11 (byte 8 + j % 4,
+    bit pair j // 4)."""
+    s = scales.astype(np.uint8)
+    lo = np.concatenate([s[:, 0:8] & 0xF, s[:, 0:8] >> 4], axis=1)                       # [nb, 16]
+    hi = np.concatenate([(s[:, 8:12] >> (2 * g)) & 3 for g in range(4)], axis=1)         # j = 4 g + (j % 4)
+    return ((lo | (hi << 4)).astype(np.int16) - 32).astype(np.int8)
+
+
+def _q23_quants(qs: np.ndarray) -> np.ndarray:
+    """[nb, 64] Q2_K / Q3_K qs -> the 2-bit fields in element order [nb, 256]: element
+    128 h + 32 j + l sits in bits 2 j .. 2 j + 1 of qs[32 h + l]."""
+    q = qs.reshape(-1, 2, 1, 32) >> (2 * np.arange(4, dtype=np.uint8)).reshape(1, 1, 4, 1)
+    return (q & 3).reshape(-1, 256)
+
+
 def dequantize(raw: np.ndarray, qtype: int, n: int) -> np.ndarray:
     raw = np.asarray(raw, dtype=np.uint8)
     if qtype == F32:
@@ -294,6 +312,19 @@ def dequantize(raw: np.ndarray, qtype: int, n: int) -> np.ndarray:
                 s = np.repeat(scl[:, h, 2 * qi:2 * qi + 2], 16, axis=1)
                 out[:, h, qi] = d * s * q
         return out.reshape(-1)
+    if qtype == Q2_K:  # w = d sc q - dmin m, (sc, m) the nibbles of the sub-block's scale byte
+        d, dmin = _f16(b[:, 80:82]), _f16(b[:, 82:84])
+        sc = (b[:, 0:16] & 0xF).astype(np.float32)
+        mn = (b[:, 0:16] >> 4).astype(np.float32)
+        q = _q23_quants(b[:, 16:80]).astype(np.float32).reshape(nb, 16, 16)
+        return ((d * sc)[:, :, None] * q - (dmin * mn)[:, :, None]).reshape(-1)
+    if qtype == Q3_K:  # w = d (s - 32) (q - 4), q = low2 | hbit << 2 (a set hmask bit: no - 4)
+        d = _f16(b[:, 108:110])
+        s = q3k_scales(b[:, 96:108]).astype(np.float32)
+        # high bit of element 128 h + 32 j + l: bit 4 h + j of hmask[l]
+        hb = (b[:, 0:32].reshape(nb, 1, 32) >> np.arange(8, dtype=np.uint8).reshape(1, 8, 1)) & 1
+        q = (_q23_quants(b[:, 32:96]) | (hb.reshape(nb, 256) << 2)).astype(np.float32) - 4
+        return ((d * s)[:, :, None] * q.reshape(nb, 16, 16)).reshape(-1)
     raise NotImplementedError(f"GGUF type {TYPE_NAMES.get(qtype, qtype)} not supported")
 
 
@@ -396,6 +427,51 @@ def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
         out[:, 128:192] = qh.reshape(nb, 64)
         out[:, 192:208] = ls.view(np.uint8)
         out[:, 208:210] = _to_f16_bytes(d)
+        return out.reshape(-1)
+    if qtype == Q2_K:
+        # per 16-element sub-block a 4-bit scale and a 4-bit min against the super-block's d / dmin;
+        # the largest scale and min land on 15, so quantising the decoded block finds the same d, dmin
+        sub = xb.reshape(nb, 16, 16)
+        mn = np.minimum(sub.min(2), 0)
+        scale = (sub.max(2) - mn) / 3
+        d = (scale.max(1) / 15).astype(np.float16).astype(np.float32)
+        dmin = ((-mn).max(1) / 15).astype(np.float16).astype(np.float32)
+        ls = np.clip(np.round(scale / np.where(d > 0, d, 1)[:, None]), 0, 15).astype(np.uint8)
+        lm = np.clip(np.round(-mn / np.where(dmin > 0, dmin, 1)[:, None]), 0, 15).astype(np.uint8)
+        eff_s = d[:, None] * ls
+        eff_m = dmin[:, None] * lm
+        q = np.clip(np.round((sub + eff_m[:, :, None]) / np.where(eff_s > 0, eff_s, 1)[:, :, None]), 0, 3)
+        q = np.where(eff_s[:, :, None] > 0, q, 0).astype(np.uint8).reshape(nb, 2, 4, 32)   # [half, bit pair, l]
+        out[:, 0:16] = ls | (lm << 4)
+        out[:, 16:80] = (q[:, :, 0] | (q[:, :, 1] << 2) | (q[:, :, 2] << 4) | (q[:, :, 3] << 6)).reshape(nb, 64)
+        out[:, 80:82] = _to_f16_bytes(d)
+        out[:, 82:84] = _to_f16_bytes(dmin)
+        return out.reshape(-1)
+    if qtype == Q3_K:
+        # signed sub-block scales: the element of largest magnitude maps to q - 4 = -4, and the
+        # sub-block scale of largest magnitude to s - 32 = -32 (both ends of the ranges, as ggml),
+        # so every value of the 6-bit field occurs and the decoded block re-quantises to itself
+        sub = xb.reshape(nb, 16, 16)
+        idx = np.abs(sub).argmax(2)
+        s = np.take_along_axis(sub, idx[:, :, None], 2)[:, :, 0] / -4.0
+        smax = np.take_along_axis(s, np.abs(s).argmax(1)[:, None], 1)[:, 0]
+        d = (smax / -32.0).astype(np.float16).astype(np.float32)
+        ls = np.clip(np.round(s / np.where(d != 0, d, 1)[:, None]), -32, 31)
+        eff = d[:, None] * ls
+        q = np.clip(np.round(sub / np.where(eff != 0, eff, 1)[:, :, None]), -4, 3)
+        q = (np.where(eff[:, :, None] != 0, q, 0) + 4).astype(np.uint8).reshape(nb, 2, 4, 32)
+        lo, hi = q & 3, q >> 2
+        hm = np.zeros((nb, 32), np.uint8)
+        for h in range(2):
+            for j in range(4):
+                hm |= hi[:, h, j] << (4 * h + j)
+        u = (ls + 32).astype(np.uint8)                                                     # 0..63
+        out[:, 0:32] = hm
+        out[:, 32:96] = (lo[:, :, 0] | (lo[:, :, 1] << 2) | (lo[:, :, 2] << 4) | (lo[:, :, 3] << 6)).reshape(nb, 64)
+        out[:, 96:104] = (u[:, 0:8] & 0xF) | ((u[:, 8:16] & 0xF) << 4)
+        hi2 = u >> 4
+        out[:, 104:108] = hi2[:, 0:4] | (hi2[:, 4:8] << 2) | (hi2[:, 8:12] << 4) | (hi2[:, 12:16] << 6)
+        out[:, 108:110] = _to_f16_bytes(d)
         return out.reshape(-1)
     raise NotImplementedError(f"quantize to {TYPE_NAMES.get(qtype, qtype)}")
 
@@ -695,9 +771,15 @@ def load_gguf_weights(model, path: str):
     def norm(name):
         return torch.from_numpy(gf.tensor_f32(name).astype(np.float32)).to(device=dev, dtype=dt)
 
+    # HIPSERVE_GGUF_Q23_NATIVE=0 (A/B): Q2_K / Q3_K tensors decoded by numpy and kept as bf16
+    q23_native = os.environ.get("HIPSERVE_GGUF_Q23_NATIVE", "1") != "0"
+    if not q23_native and dev.type == "cuda" and any(t.type in (Q2_K, Q3_K) for t in gf.tensors.values()):
+        log.info("GGUF %s: HIPSERVE_GGUF_Q23_NATIVE=0, Q2_K / Q3_K tensors dequantised to %s at load", path, dt)
+
     def matrix(*names):
         infos = [gf.tensors[n] for n in names]
-        if all(i.type in (F32, F16, BF16) for i in infos) or dev.type != "cuda":
+        if all(i.type in (F32, F16, BF16) for i in infos) or dev.type != "cuda" or \
+                (not q23_native and any(i.type in (Q2_K, Q3_K) for i in infos)):
             return torch.cat([dense(n) for n in names], 0) if len(names) > 1 else dense(names[0])
         return QuantWeight.from_gguf(gf, names, dev)
 
@@ -719,6 +801,8 @@ def load_gguf_weights(model, path: str):
 
         rows = sum(i.shape[1] for i in infos)
         name = lambda t: TYPE_NAMES.get(t, str(t))  # noqa: E731
+        if not q23_native and any(i.type in (Q2_K, Q3_K) for i in infos):
+            return "HIPSERVE_GGUF_Q23_NATIVE=0"
         if len({i.type for i in infos}) != 1:
             return "gate and up differ in format (" + " / ".join(name(i.type) for i in infos) + ")"
         if not QuantMoE.supported(KERNEL_QT.get(infos[0].type, -1), rows, K):
@@ -791,18 +875,27 @@ def load_gguf_weights(model, path: str):
             lw.q_norm = torch.from_numpy(gf.tensor_f32(p + "attn_q_norm.weight").astype(np.float32)).to(dev)
             lw.k_norm = torch.from_numpy(gf.tensor_f32(p + "attn_k_norm.weight").astype(np.float32)).to(dev)
         model.layers.append(lw)
-    from ..ops.quant import quant_linear
+    from ..ops.quant import KERNEL_QT, QuantMoE, quant_linear
 
+    # the Q2_K / Q3_K projections and expert stacks resident as tiled blocks only
+    q23 = (KERNEL_QT[Q2_K], KERNEL_QT[Q3_K])
+    mats = [model.lm_head] + [w for lw in model.layers for w in (lw.wqkv, lw.wo, lw.wgu, lw.wd)]
+    held = [p.nbytes for w in mats if isinstance(w, QuantWeight) for p in w.parts if p.kqt in q23]
+    held += [w.q.numel() for lw in model.layers for w in (lw.w13, lw.w2) if isinstance(w, QuantMoE) and w.kqt in q23]
+    if held:
+        log.info("GGUF %s: %d Q2_K / Q3_K matrices and expert stacks kept as tiled blocks, %.1f MB", path, len(held),
+                 sum(held) / 1e6)
     model.quant_linear = quant_linear
     model.gguf = gf
     return gf
 
 
 def write_synthetic_llama_gguf(path: str, cfg, qtype: int = Q8_0, seed: int = 0, std: float = 0.05,
-                               vocab_tokens: list[str] | None = None, mixed_k: bool = False):
+                               vocab_tokens: list[str] | None = None, mixed_k: bool = False, embd_type: int = F16):
     """Write a random-weight llama GGUF (tests and GGUF-tier benchmarks; no
     network means no real checkpoints). ``mixed_k`` mimics Q4_K_M: attn_v and
-    ffn_down in Q6_K, the rest in Q4_K."""
+    ffn_down in Q6_K, the rest in Q4_K. ``embd_type``: the ggml type of
+    ``token_embd.weight`` (real Q2_K / Q3_K files hold it quantised)."""
     rng = np.random.default_rng(seed)
     H, I, D = cfg.hidden_size, cfg.intermediate_size, cfg.head_dim
     nq, nkv, V = cfg.num_heads, cfg.num_kv_heads, cfg.vocab_size
@@ -824,7 +917,7 @@ def write_synthetic_llama_gguf(path: str, cfg, qtype: int = Q8_0, seed: int = 0,
           "tokenizer.ggml.bos_token_id": 1, "tokenizer.ggml.eos_token_id": 2}
     k4 = Q4_K if mixed_k else qtype
     k6 = Q6_K if mixed_k else qtype
-    tensors = [("token_embd.weight", r(V, H), F16), ("output_norm.weight", 1 + r(H), F32),
+    tensors = [("token_embd.weight", r(V, H), embd_type), ("output_norm.weight", 1 + r(H), F32),
                ("output.weight", r(V, H), k6)]
     for i in range(cfg.num_layers):
         n = gguf_name_map(i)

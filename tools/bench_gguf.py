@@ -35,6 +35,9 @@ SHAPES = {  # Q4_K_M: attn_v / ffn_down / output in Q6_K
 }
 
 
+GGUF_KINDS = {"q4_1": G.Q4_1, "q2_k": G.Q2_K, "q3_k": G.Q3_K, "q4_k": G.Q4_K}
+
+
 def _time(fn, reps=20, graph_reps=10):
     """Device µs per call: ``reps`` calls captured in one hipGraph (no host launch
     cost, like the engine's decode step), replayed ``graph_reps`` times."""
@@ -65,10 +68,11 @@ def main():
     ap.add_argument("--only", nargs="*", default=None)
     ap.add_argument("--splits", type=int, nargs="*", default=None)
     ap.add_argument("--fp8", action="store_true", help="FP8 e4m3 per-channel weights of the same shapes")
-    ap.add_argument("--kind", default=None, choices=["int4", "int8", "q4_1"],
+    ap.add_argument("--kind", default=None, nargs="+", choices=["int4", "int8"] + sorted(GGUF_KINDS),
                     help="every part of the same shapes in ONE format: int4 (group 128, asymmetric: the AWQ / "
-                         "compressed-tensors W4A16 layout), int8 (group 128) or the GGUF Q4_1 blocks (INT4's "
-                         "2,560-byte chunk, the same kernel family)")
+                         "compressed-tensors W4A16 layout), int8 (group 128) or GGUF blocks of one type (q4_1: "
+                         "INT4's 2,560-byte chunk; q2_k / q3_k next to q4_k: the same shapes in one run). "
+                         "Several kinds run one after the other per projection")
     ap.add_argument("--prefill", action="store_true",
                     help="M > 64: the prefill GEMM from the blocks (qpf) and the M-tiled dequant-MFMA kernel vs "
                          "dequant-to-scratch + hipBLASLt vs a bf16 shadow")
@@ -79,7 +83,7 @@ def main():
     a = ap.parse_args()
     load_library()
     rng = np.random.default_rng(0)
-    for name, specs in SHAPES.items():
+    for name, specs, kind in [(n, s, k) for n, s in SHAPES.items() for k in (a.kind or [None])]:
         if a.only and name not in a.only:
             continue
         if a.fp8:
@@ -90,12 +94,12 @@ def main():
                 parts.append(Q.QuantPart.from_fp8((w / sc).to(torch.float8_e4m3fn), sc, "cuda"))
                 del w
             qw = Q.QuantWeight(parts)
-        elif a.kind in ("int4", "int8"):
+        elif kind in ("int4", "int8"):
             parts = []
             for _, n, k in specs:
-                bits = 4 if a.kind == "int4" else 8
+                bits = 4 if kind == "int4" else 8
                 u = torch.randint(0, 1 << bits, (n, k), device="cuda", dtype=torch.uint8)
-                if a.kind == "int4":  # |w| ~ 0.02
+                if kind == "int4":  # |w| ~ 0.02
                     sc = torch.full((n, k // 128), 0.00375, device="cuda")
                     parts.append(Q.QuantPart.from_int4(u, sc, torch.randint(0, 16, (n, k // 128), device="cuda"), "cuda"))
                 else:
@@ -103,8 +107,8 @@ def main():
                     parts.append(Q.QuantPart.from_int8(u, sc, torch.randint(-8, 8, (n, k // 128), device="cuda"), "cuda"))
                 del u
             qw = Q.QuantWeight(parts)
-        elif a.kind == "q4_1":
-            raws = [(G.Q4_1, n, k, Q.random_blocks(rng, G.Q4_1, n, k)) for _, n, k in specs]
+        elif kind in GGUF_KINDS:
+            raws = [(GGUF_KINDS[kind], n, k, Q.random_blocks(rng, GGUF_KINDS[kind], n, k)) for _, n, k in specs]
             qw = Q.QuantWeight.from_raw(raws, "cuda")
             del raws
         else:
@@ -164,7 +168,7 @@ def main():
                 rows.append((f"v2_S{Sx}", Sx, timed(lambda qs: Q._launch_v2(e, ws, x, qw, Sx, x16, qs))))
             del copies
             for kern, S, us in rows:
-                print(json.dumps({"proj": name, "fmt": a.kind or ("fp8" if a.fp8 else "q4_k_m"), "M": M, "kernel": kern,
+                print(json.dumps({"proj": name, "fmt": kind or ("fp8" if a.fp8 else "q4_k_m"), "M": M, "kernel": kern,
                                   "splits": S, "us": round(us, 2),
                                   "weight_MB": round(qw.nbytes / 1e6, 2), "cold": a.cold,
                                   "TBps": round(qw.nbytes / us / 1e6, 3),

@@ -3,7 +3,7 @@ MoE layer (``--model``: Qwen3-30B-A3B, Mixtral-8x7B) at decode batch sizes: w13 
 token rows) and w2 (slot rows, split over K), INT8 (per-32-k scale / offset table) vs
 INT8C (per-channel, row scale in the epilogue) vs INT4 (``int4``: group 128, asymmetric,
 the AWQ / compressed-tensors W4A16 layout) vs FP8 vs the GGUF block formats (q4_0,
-q4_1, q8_0, q4_k, q5_k, q6_k: random valid blocks), at several K splits. Graph-timed over
+q4_1, q8_0, q2_k, q3_k, q4_k, q5_k, q6_k: random valid blocks), at several K splits. Graph-timed over
 ``--layers`` distinct layers (their experts exceed the MALL); TB/s counts the bytes of the
 experts that received tokens (for GGUF formats: the bytes of their blocks).
 
@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_ops import graph_time  # noqa: E402
 
 
-GGUF_KINDS = {"q4_0": 2, "q4_1": 3, "q8_0": 8, "q4_k": 12, "q5_k": 13, "q6_k": 14}  # ggml type ids
+GGUF_KINDS = {"q4_0": 2, "q4_1": 3, "q8_0": 8, "q2_k": 10, "q3_k": 11, "q4_k": 12, "q5_k": 13, "q6_k": 14}  # ggml type ids
 _blocks: dict = {}
 
 
