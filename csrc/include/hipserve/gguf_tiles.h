@@ -1,13 +1,13 @@
-// Shared device helpers of the tiled quantised-weight kernels (gguf_mfma.hip: the v2
-// decode GEMM, K15 / qpg prefill, dequant; fp8_decode.hip):
+// Device helpers of the tiled quantised-weight kernels (gguf_mfma.hip: the v2 decode
+// GEMM, K15 / qpg prefill, expert GEMM, dequant):
 // the per-format tiled chunk layouts, raw loads, and the subnormal-integer dequant.
 #pragma once
 
 #include "hipserve/common.h"
+#include "hipserve/quant_formats.h"
 
 namespace hipserve {
 namespace gq {
-
 
 // GGUF block formats + FP8 e4m3 weights (per-row scale; FP8B adds 128 x 128 block
 // scales, the block-FP8 checkpoints)
@@ -24,17 +24,7 @@ namespace gq {
 // Q2_K / Q3_K: the 2-bit / 3-bit K-quants (16-element sub-blocks like Q6_K): Q2_K
 // w = d sc q - dmin m with 4-bit sc, m per sub-block; Q3_K w = d (s - 32) (q - 4) with a
 // 6-bit scale s per sub-block and the third bit of q in a separate plane (hmask).
-enum { Q4_0 = 0, Q4_1 = 1, Q8_0 = 2, Q4_K = 3, Q5_K = 4, Q6_K = 5, FP8 = 6, FP8B = 7, INT8 = 8, INT8C = 9,
-       INT4 = 10, Q2_K = 11, Q3_K = 12 };
-// Properties of a format by name, never by its place in the enum:
-// the GGUF block formats (scales inside the chunk, subnormal-integer dequant)
-constexpr bool gguf_block_format(int qt) {
-  return qt == Q4_0 || qt == Q4_1 || qt == Q8_0 || qt == Q4_K || qt == Q5_K || qt == Q6_K || qt == Q2_K || qt == Q3_K;
-}
-// the formats the block prefill GEMM (qpg_kernel) is built for
-constexpr bool qpg_format(int qt) {
-  return qt == Q4_0 || qt == Q4_1 || qt == Q8_0 || qt == Q4_K || qt == Q5_K || qt == Q6_K;
-}
+// (the enum and what is true of each format: quant_formats.h, one table row per format)
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -66,6 +56,11 @@ HS_DEVICE f16x8 frag(h2 a, h2 b, h2 c, h2 d) {
 HS_DEVICE void nib_pairs(unsigned w, int sh, unsigned& p02, unsigned& p13) {
   p02 = ((w >> sh) & 0x000F000Fu) | kMagic;
   p13 = ((w >> (sh + 8)) & 0x000F000Fu) | kMagic;
+}
+// bytes (0, 2) and (1, 3) of w -> 1024 + u pairs
+HS_DEVICE void byte_pairs(unsigned w, unsigned& p02, unsigned& p13) {
+  p02 = (w & 0x00FF00FFu) | kMagic;
+  p13 = ((w >> 8) & 0x00FF00FFu) | kMagic;
 }
 
 struct Raw {
@@ -101,14 +96,10 @@ struct Raw {
 //         in-kernel 6-bit unpack is the VALU cost that bounds this kernel family); its
 //         hmask bytes 16 (g & 1) .. + 15 hold the third bit of step s at bit 4 (g >> 1) + (s >> 1)
 template <int QT>
-constexpr int chunk_bytes() {
-  return QT == Q2_K ? 1344 : QT == Q3_K ? 1824
-       : QT == Q4_K ? 2304 : QT == Q5_K ? 2816 : QT == Q6_K ? 3360 : QT == Q8_0 ? 4352 : QT == Q4_0 ? 2304
-       : QT == Q4_1 || QT == INT4 ? 2560 : QT == FP8 || QT == INT8C ? 4096 : QT == FP8B ? 4224 : 4608;
-}
+constexpr int chunk_bytes() { return quant_format(QT).chunk_bytes; }
 // formats whose per-row scale (Part::rs) multiplies the accumulators in the epilogue
 template <int QT>
-constexpr bool row_scaled() { return QT == FP8 || QT == FP8B || QT == INT8C; }
+constexpr bool row_scaled() { return quant_format(QT).row_scaled; }
 
 struct Part {
   const unsigned char* q;
@@ -255,7 +246,7 @@ HS_DEVICE int kbase(int g, int s) {
 // 1024, 8: d sc < 65504 / 2^16 ~ 0.9995; Q3_K (q < 8) 7: |d (s - 32)| < 65504 / 2^17 ~ 0.4998.
 // These two have no v1 kernel: a weight beyond the range is held as bf16 (QuantWeight.from_gguf).
 template <int QT>
-constexpr int sub_shift() { return QT == Q2_K ? 8 : QT == Q3_K ? 7 : QT == Q5_K ? 5 : QT == Q6_K ? 4 : QT == Q8_0 ? 2 : 6; }
+constexpr int sub_shift() { return quant_format(QT).sub_shift; }
 template <int QT>
 constexpr float sub_up() {
   return gguf_block_format(QT) ? (float)(1 << (24 - sub_shift<QT>())) : 1.f;
@@ -372,21 +363,14 @@ struct Dec {
   }
 
   HS_DEVICE f16x8 ints(const Raw& r, int g, int s) const {
-    if constexpr (QT == INT8C) {  // u - 128 exact: (1024 + u) - 1152
+    if constexpr (QT == INT8C || QT == INT8) {
       const u32x4 qv[4] = {r.v[0], r.v[1], r.v[2], r.v[3]};
-      const unsigned wa = qv[s >> 1][2 * (s & 1)], wb = qv[s >> 1][2 * (s & 1) + 1];
-      const h2 cc = splat(-1152.f);
-      const unsigned p0 = (wa & 0x00FF00FFu) | kMagic, p1 = ((wa >> 8) & 0x00FF00FFu) | kMagic;
-      const unsigned p2 = (wb & 0x00FF00FFu) | kMagic, p3 = ((wb >> 8) & 0x00FF00FFu) | kMagic;
-      return frag(as_h2(p0) + cc, as_h2(p1) + cc, as_h2(p2) + cc, as_h2(p3) + cc);
-    }
-    if constexpr (QT == INT8) {  // u - 128 - zp, exact
-      const u32x4 qv[4] = {r.v[0], r.v[1], r.v[2], r.v[3]};
-      const unsigned wa = qv[s >> 1][2 * (s & 1)], wb = qv[s >> 1][2 * (s & 1) + 1];
-      const h2 cc = s < 4 ? cA : cB;
-      const unsigned p0 = (wa & 0x00FF00FFu) | kMagic, p1 = ((wa >> 8) & 0x00FF00FFu) | kMagic;
-      const unsigned p2 = (wb & 0x00FF00FFu) | kMagic, p3 = ((wb >> 8) & 0x00FF00FFu) | kMagic;
-      return frag(as_h2(p0) + cc, as_h2(p1) + cc, as_h2(p2) + cc, as_h2(p3) + cc);
+      // INT8C: u - 128 exact: (1024 + u) - 1152; INT8: u - 128 - zp, exact
+      const h2 cc = QT == INT8C ? splat(-1152.f) : s < 4 ? cA : cB;
+      unsigned p[4];
+      byte_pairs(qv[s >> 1][2 * (s & 1)], p[0], p[1]);
+      byte_pairs(qv[s >> 1][2 * (s & 1) + 1], p[2], p[3]);
+      return frag(as_h2(p[0]) + cc, as_h2(p[1]) + cc, as_h2(p[2]) + cc, as_h2(p[3]) + cc);
     }
     if constexpr (QT == INT4) {  // u - z, exact: (1024 + u) - (1024 + z)
       const u32x4 qs[2] = {r.v[0], r.v[1]};
@@ -456,10 +440,8 @@ struct Dec {
     } else if constexpr (QT == Q8_0) {
       const u32x4 qv[4] = {r.v[0], r.v[1], r.v[2], r.v[3]};
       const unsigned wa = qv[s >> 1][2 * (s & 1)] ^ 0x80808080u, wb = qv[s >> 1][2 * (s & 1) + 1] ^ 0x80808080u;
-      p[0] = (wa & 0x00FF00FFu) | kMagic;
-      p[1] = ((wa >> 8) & 0x00FF00FFu) | kMagic;
-      p[2] = (wb & 0x00FF00FFu) | kMagic;
-      p[3] = ((wb >> 8) & 0x00FF00FFu) | kMagic;
+      byte_pairs(wa, p[0], p[1]);
+      byte_pairs(wb, p[2], p[3]);
       z = (_Float16)1152.f;  // int8 value
     } else {  // Q4_0 / Q4_1: block (s >> 2); elements 0-15 low nibbles, 16-31 high
       const u32x4 v[2] = {r.v[0], r.v[1]};
@@ -547,16 +529,11 @@ struct Dec {
     if constexpr (gguf_block_format(QT)) {
       const u32x4 qu = __builtin_bit_cast(u32x4, sub_ints(r, g, s));
       h2 dd, cc;
-      if constexpr (QT == Q6_K || QT == Q3_K) {
+      if constexpr (QT == Q6_K || QT == Q3_K || QT == Q2_K) {  // Q2_K: Q4_K's form, a scale / min pair per two steps
         float d, c;
         scale(r, g, s, d, c);
         dd = splat(d * sub_up<QT>());
-        cc = splat(sub_zero<QT>() * (float)(_Float16)d);
-      } else if constexpr (QT == Q2_K) {  // Q4_K's form with a scale / min pair per two steps
-        float d, c;
-        scale(r, g, s, d, c);
-        dd = splat(d * sub_up<QT>());
-        cc = splat(c);
+        cc = splat(QT == Q2_K ? c : sub_zero<QT>() * (float)(_Float16)d);
       } else if constexpr (QT == Q4_0 || QT == Q4_1) {
         dd = (s >> 2) ? dB : dA;
         cc = (s >> 2) ? cB : cA;
@@ -565,44 +542,23 @@ struct Dec {
         cc = s < 4 ? cA : cB;
       }
       return frag(as_h2(qu[0]) * dd + cc, as_h2(qu[1]) * dd + cc, as_h2(qu[2]) * dd + cc, as_h2(qu[3]) * dd + cc);
-    }
-    if constexpr (QT == INT8) {  // (1024 + u + off) * s: exact integer, one rounding
+    } else if constexpr (QT == FP8 || QT == INT8C) {
+      return ints(r, g, s);  // row scale in the epilogue
+    } else if constexpr (QT == INT8) {  // (1024 + u + off) * s: exact integer, one rounding
+      // (not built from ints() like INT4's: the compiler then schedules the decode GEMM differently)
       const u32x4 qv[4] = {r.v[0], r.v[1], r.v[2], r.v[3]};
-      const unsigned wa = qv[s >> 1][2 * (s & 1)], wb = qv[s >> 1][2 * (s & 1) + 1];
       const h2 dd = s < 4 ? dA : dB, cc = s < 4 ? cA : cB;
-      const unsigned p0 = (wa & 0x00FF00FFu) | kMagic, p1 = ((wa >> 8) & 0x00FF00FFu) | kMagic;
-      const unsigned p2 = (wb & 0x00FF00FFu) | kMagic, p3 = ((wb >> 8) & 0x00FF00FFu) | kMagic;
-      return frag((as_h2(p0) + cc) * dd, (as_h2(p1) + cc) * dd, (as_h2(p2) + cc) * dd, (as_h2(p3) + cc) * dd);
-    }
-    if constexpr (QT == INT4) {  // (1024 + u + off) * s, as INT8: no scale-range limit
-      const u32x4 qu = __builtin_bit_cast(u32x4, ints(r, g, s));
-      const h2 dd = s < 4 ? dA : dB;
-      return frag(as_h2(qu[0]) * dd, as_h2(qu[1]) * dd, as_h2(qu[2]) * dd, as_h2(qu[3]) * dd);
-    }
-    const f16x8 q = ints(r, g, s);
-    if constexpr (QT == FP8 || QT == INT8C) return q;  // row scale in the epilogue
-    if constexpr (QT == FP8B) {
-      const u32x4 qu = __builtin_bit_cast(u32x4, q);
-      return frag(as_h2(qu[0]) * dA, as_h2(qu[1]) * dA, as_h2(qu[2]) * dA, as_h2(qu[3]) * dA);
-    }
-    h2 dd, cc;
-    if constexpr (QT == Q6_K) {
-      float d, c;
-      scale(r, g, s, d, c);
-      dd = splat(d);
-      cc = h2{(_Float16)0.f, (_Float16)0.f};
-    } else if constexpr (QT == Q4_0 || QT == Q4_1) {
-      dd = (s >> 2) ? dB : dA;
-      cc = (s >> 2) ? cB : cA;
+      unsigned p[4];
+      byte_pairs(qv[s >> 1][2 * (s & 1)], p[0], p[1]);
+      byte_pairs(qv[s >> 1][2 * (s & 1) + 1], p[2], p[3]);
+      return frag((as_h2(p[0]) + cc) * dd, (as_h2(p[1]) + cc) * dd, (as_h2(p[2]) + cc) * dd, (as_h2(p[3]) + cc) * dd);
     } else {
-      dd = s < 4 ? dA : dB;
-      cc = s < 4 ? cA : cB;
-    }
-    const u32x4 qu = __builtin_bit_cast(u32x4, q);
-    if constexpr (QT == Q6_K || QT == Q8_0 || QT == Q4_0)  // no min term
+      // INT4: (1024 + u + off) * s, as INT8: no scale-range limit; FP8B: the lane's block scale
+      static_assert(QT == INT4 || QT == FP8B, "Dec::step: no body for this format");
+      const u32x4 qu = __builtin_bit_cast(u32x4, ints(r, g, s));
+      const h2 dd = QT == FP8B || s < 4 ? dA : dB;
       return frag(as_h2(qu[0]) * dd, as_h2(qu[1]) * dd, as_h2(qu[2]) * dd, as_h2(qu[3]) * dd);
-    else
-      return frag(as_h2(qu[0]) * dd + cc, as_h2(qu[1]) * dd + cc, as_h2(qu[2]) * dd + cc, as_h2(qu[3]) * dd + cc);
+    }
   }
 };
 

@@ -79,7 +79,8 @@ void launch_penalty_init(int* counts, unsigned int* seen, int V, const int* slot
 void launch_top_logprobs(const void* logits, bool is_bf16, long stride, int rows, int V, const int* nreq,
                          int* out_ids, float* out_lp, int K, hipStream_t s);
 
-// gguf.hip — qtype: 0 Q4_0, 1 Q4_1, 2 Q8_0, 3 Q4_K, 4 Q5_K, 5 Q6_K (repacked layouts)
+// gguf.hip (v1) — qtype: its own QT_* ids 0 Q4_0, 1 Q4_1, 2 Q8_0, 3 Q4_K, 4 Q5_K, 5 Q6_K (repacked
+// layouts); the tiled kernels of gguf_mfma.hip below take the ids of quant_formats.h
 void launch_gguf_gemm(void* out, float* ws, const void* x, long x_stride, long out_stride,
                       const void* q, const void* d, const void* m, int qtype, long row_bytes,
                       int M, int N, int K, int splits, hipStream_t s);
@@ -90,12 +91,11 @@ void launch_gguf_dequant(void* out, const void* q, const void* d, const void* m,
 // ws[S, M, Ntot] fp32 partials. M <= 64, parts' rows % 16 == 0.
 struct GgufPart {
   const void* q;
-  const float* rs;  // FP8 formats: per-row output scale
-  int qtype;
+  const float* rs;  // row-scaled formats: per-row output scale
+  int qtype;        // kernel format id (quant_formats.h)
   int rows;
   int col;
 };
-int gguf_tiled_chunk_bytes(int qtype);
 // x16 (optional, M <= 64): x as f16 in the kernel's staging pair order {0,2,1,3,4,6,5,7}
 // per aligned 8-run, row stride x_stride (decode_fused.hip producers write it)
 void launch_gguf_gemm_parts(void* out, long out_stride, float* ws, const void* x, long x_stride,
@@ -114,8 +114,7 @@ bool launch_gguf_prefill(int epi, void* out, long ldo, const void* x16, const fl
 void launch_x_f16_pairs(void* x16, float* rsc, const void* x, long ldx, int M, int K, hipStream_t s);
 // quantised MoE experts (tiled layout per expert, stacked [E][N/16][K/256][chunk]) over
 // moe_align tiles of 16/32/64 slots: out[slot, N] bf16 (S == 1) or ws[S, nslots, N] fp32.
-// qtype: FP8 (rs [E, N]), INT8 / INT8C or INT4 (the checkpoint expert formats), or a GGUF block format. Returns false for an
-// unsupported tile / qtype.
+// qtype: a format with an expert body (quant_formats.h moe; rs [E, N] if row-scaled), else false, as for other tiles.
 bool launch_qmoe_gemm(void* out, long out_stride, float* ws, const void* x, long x_stride, const void* q,
                       const float* rs, int qtype, long w_estride, long rs_estride, const int* slots,
                       const int* tile_expert, int tiles_cap, int tile, int gather_k, int N, int K, int S,

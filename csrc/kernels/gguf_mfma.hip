@@ -40,7 +40,6 @@ namespace hipserve {
 namespace {
 using namespace gq;
 
-
 // f16 range of the staged x: a value beyond +-65504 (bf16 activations reach ~3e38;
 // Gemma-family hidden states are known to exceed the f16 range) converts to +-inf
 // and is caught, not clamped: the inf makes every accumulator of its x row
@@ -397,7 +396,7 @@ void launch_t(void* out, long out_stride, float* ws, const void* x, long x_strid
 // (profiles/q2k_q3k_resources.md)
 template <int QT, int MT>
 constexpr int qmoe_waves() {
-  return gguf_block_format(QT) || QT == INT8 || QT == INT4 ? 1 : MT == 1 ? 4 : 1;
+  return !row_scaled<QT>() ? 1 : MT == 1 ? 4 : 1;  // row-scaled: no scale table in the chunk
 }
 template <int QT, int MT, int RT, int NWAVES>
 __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(qmoe_waves<QT, MT>())))
@@ -426,16 +425,13 @@ void moe_launch_t(void* out, long out_stride, float* ws, const void* x, long x_s
   const int ysplit = (nsb + per - 1) / per;
   // GLU: 4 waves x one gate group (+ its up group) = 64 act columns per workgroup
   const int xt = moe.glu ? (N / 2 + 63) / 64 : (N + 127) / 128;
-  if (tile == 16) {
-    const dim3 grid(xt, ysplit, tiles_cap);
+  const dim3 grid(tile == 64 ? (N + 127) / 128 : xt, ysplit, tiles_cap);
+  if (tile == 16)
     qmoe_kernel<QT, 1, 2, kWaves><<<grid, 64 * kWaves, 0, s>>>(o, out_stride, ws, xi, x_stride, qq, rs, moe, N, K, per);
-  } else if (tile == 32) {
-    const dim3 grid(xt, ysplit, tiles_cap);
+  else if (tile == 32)
     qmoe_kernel<QT, 2, 2, kWaves><<<grid, 64 * kWaves, 0, s>>>(o, out_stride, ws, xi, x_stride, qq, rs, moe, N, K, per);
-  } else {
-    const dim3 grid((N + 127) / 128, ysplit, tiles_cap);
+  else
     qmoe_kernel<QT, 4, 1, 8><<<grid, 512, 0, s>>>(o, out_stride, ws, xi, x_stride, qq, rs, moe, N, K, per);
-  }
 }
 
 // ---------------------------------------------------------------- tiled -> bf16
@@ -825,25 +821,6 @@ __global__ __launch_bounds__(256) void x_f16_pairs_kernel(unsigned short* __rest
 
 }  // namespace
 
-int gguf_tiled_chunk_bytes(int qtype) {
-  switch (qtype) {
-    case Q4_0: return chunk_bytes<Q4_0>();
-    case Q4_1: return chunk_bytes<Q4_1>();
-    case Q8_0: return chunk_bytes<Q8_0>();
-    case Q4_K: return chunk_bytes<Q4_K>();
-    case Q5_K: return chunk_bytes<Q5_K>();
-    case Q6_K: return chunk_bytes<Q6_K>();
-    case FP8: return chunk_bytes<FP8>();
-    case FP8B: return chunk_bytes<FP8B>();
-    case INT8: return chunk_bytes<INT8>();
-    case INT8C: return chunk_bytes<INT8C>();
-    case INT4: return chunk_bytes<INT4>();
-    case Q2_K: return chunk_bytes<Q2_K>();
-    case Q3_K: return chunk_bytes<Q3_K>();
-  }
-  return 0;
-}
-
 // Parts in the tiled layout. ws != nullptr: fp32 partials [S, M, Ntot]; else bf16
 // out (S must be 1). Parts of one format, or of the pairs Q4_K+Q6_K / Q5_K+Q6_K
 // (the K-quant mixes), share one launch; any other mix launches per format.
@@ -881,21 +858,10 @@ void launch_gguf_gemm_parts(void* out, long out_stride, float* ws, const void* x
   }
   for (int f = 0; f < nf; ++f) {
     const Parts P = table(fmts[f], fmts[f], tiles);
-    switch (fmts[f]) {
-      case Q4_0: launch_t<Q4_0, Q4_0>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case Q4_1: launch_t<Q4_1, Q4_1>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case Q8_0: launch_t<Q8_0, Q8_0>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case Q4_K: launch_t<Q4_K, Q4_K>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case Q5_K: launch_t<Q5_K, Q5_K>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case Q6_K: launch_t<Q6_K, Q6_K>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case FP8: launch_t<FP8, FP8>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case FP8B: launch_t<FP8B, FP8B>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case INT8: launch_t<INT8, INT8>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case INT8C: launch_t<INT8C, INT8C>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case INT4: launch_t<INT4, INT4>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case Q2_K: launch_t<Q2_K, Q2_K>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-      case Q3_K: launch_t<Q3_K, Q3_K>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16); break;
-    }
+    dispatch_format(fmts[f], [&](auto qt) {
+      constexpr int QT = decltype(qt)::value;
+      launch_t<QT, QT>(out, out_stride, ws, x, x_stride, P, tiles, M, Ntot, K, S, s, x16);
+    });
   }
 }
 
@@ -907,21 +873,15 @@ bool launch_qmoe_gemm(void* out, long out_stride, float* ws, const void* x, long
   // GLU epilogue: the 16 / 32-slot bodies (two row groups per wave), whole K, N / 2 % 16
   if (glu && (tile == 64 || S != 1 || ws != nullptr || (N / 2) % 16)) return false;
   const MoeQ moe{slots, tile_expert, w_estride, rs_estride, gather_k, tiles_cap * tile, kmajor ? 1 : 0, glu};
-  switch (qtype) {
-    case Q4_0: moe_launch_t<Q4_0>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case Q4_1: moe_launch_t<Q4_1>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case Q8_0: moe_launch_t<Q8_0>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case Q4_K: moe_launch_t<Q4_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case Q5_K: moe_launch_t<Q5_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case Q6_K: moe_launch_t<Q6_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case FP8: moe_launch_t<FP8>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case INT8: moe_launch_t<INT8>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case INT8C: moe_launch_t<INT8C>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case INT4: moe_launch_t<INT4>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case Q2_K: moe_launch_t<Q2_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-    case Q3_K: moe_launch_t<Q3_K>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s); return true;
-  }
-  return false;
+  bool taken = false;  // FP8B has no expert body (moe_format): block-FP8 MoE checkpoints are not served
+  dispatch_format(qtype, [&](auto qt) {
+    constexpr int QT = decltype(qt)::value;
+    if constexpr (moe_format(QT)) {
+      moe_launch_t<QT>(out, out_stride, ws, x, x_stride, q, rs, moe, tiles_cap, tile, N, K, S, s);
+      taken = true;
+    }
+  });
+  return taken;
 }
 
 // Prefill GEMM over tiled GGUF parts (qpg_kernel) on x16 / rsc from launch_x_f16_pairs
@@ -969,13 +929,10 @@ bool launch_gguf_prefill(int epi, void* out, long ldo, const void* x16, const fl
       tiles += (parts[i].rows + QF_ROWS - 1) / QF_ROWS;
     }
     A.tiles_n = glu ? (parts[0].rows + QF_ROWS / 2 - 1) / (QF_ROWS / 2) : tiles;
-#define QF_CASE(QT_)          \
-  if (fa == QT_) {              \
-    qpg_launch<QT_>(epi, A, s); \
-    return;                     \
-  }
-    QF_CASE(Q4_0) QF_CASE(Q4_1) QF_CASE(Q8_0) QF_CASE(Q4_K) QF_CASE(Q5_K) QF_CASE(Q6_K)
-#undef QF_CASE
+    dispatch_format(fa, [&](auto qt) {
+      constexpr int QT = decltype(qt)::value;
+      if constexpr (qpg_format(QT)) qpg_launch<QT>(epi, A, s);
+    });
   };
   if (glu && nf != 1) return false;
   for (int f = 0; f < nf; ++f) run(fmts[f]);
@@ -996,21 +953,9 @@ void launch_gguf_dequant_tiled(void* out, const void* q, const float* rs, int qt
   const dim3 grid((unsigned)((items + 3) / 4)), block(256);
   auto* o = static_cast<unsigned short*>(out);
   auto* qq = static_cast<const unsigned char*>(q);
-  switch (qtype) {
-    case Q4_0: dequant_tiled_kernel<Q4_0><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case Q4_1: dequant_tiled_kernel<Q4_1><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case Q8_0: dequant_tiled_kernel<Q8_0><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case Q4_K: dequant_tiled_kernel<Q4_K><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case Q5_K: dequant_tiled_kernel<Q5_K><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case Q6_K: dequant_tiled_kernel<Q6_K><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case FP8: dequant_tiled_kernel<FP8><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case FP8B: dequant_tiled_kernel<FP8B><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case INT8: dequant_tiled_kernel<INT8><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case INT8C: dequant_tiled_kernel<INT8C><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case INT4: dequant_tiled_kernel<INT4><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case Q2_K: dequant_tiled_kernel<Q2_K><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-    case Q3_K: dequant_tiled_kernel<Q3_K><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0); break;
-  }
+  dispatch_format(qtype, [&](auto qt) {
+    dequant_tiled_kernel<decltype(qt)::value><<<grid, block, 0, s>>>(o, qq, rs, N / 16, K, pack, nrows, kmajor ? 1 : 0);
+  });
 }
 
 }  // namespace hipserve

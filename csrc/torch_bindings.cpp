@@ -7,7 +7,10 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <sstream>
+
 #include "hipserve/kernels.h"
+#include "hipserve/quant_formats.h"
 
 namespace {
 
@@ -311,8 +314,26 @@ void gguf_gemm(at::Tensor& out, const at::Tensor& x, const at::Tensor& q, const 
 // parts in the tiled layout (one uint8 tensor [N/16, K/256, chunk] each), their
 // formats / rows / output columns. ws.numel() > 0: fp32 partials [S_actual, M, Ntot]
 // (returned S_actual = ceil(nsb / ceil(nsb / S))); else bf16 out [M, >= Ntot], S == 1.
-// kernel formats with a per-row fp32 output scale: FP8, FP8B, INT8C (gguf_tiles.h row_scaled)
-static bool row_scaled_qt(int64_t qt) { return qt == 6 || qt == 7 || qt == 9; }
+using hipserve::gq::QuantFormat;
+
+// quant_formats.h as text, "NAME id chunk_bytes sub_shift gguf row_scaled prefill moe" per line:
+// for the error messages, and as an op for the cross-check against hipserve/ops/quant.py
+static std::string quant_formats() {
+  std::ostringstream o;
+  for (int id : hipserve::gq::kQuantFormatIds) {
+    const QuantFormat f = hipserve::gq::quant_format(id);
+    o << f.name << ' ' << f.id << ' ' << f.chunk_bytes << ' ' << f.sub_shift << ' ' << f.gguf << ' ' << f.row_scaled
+      << ' ' << f.prefill << ' ' << f.moe << '\n';
+  }
+  return o.str();
+}
+// the table row of a tiled op's kernel qtype (moe: of a format with an expert body)
+static QuantFormat tiled_format(int64_t qtype, const char* op, bool moe = false) {
+  const QuantFormat f = hipserve::gq::quant_format(qtype == (int)qtype ? (int)qtype : -1);
+  TORCH_CHECK(f.id >= 0 && (f.moe || !moe), op, ": kernel qtype ", qtype, moe ? " has no expert body" : " is unknown",
+              "; name id chunk sub_shift gguf row_scaled prefill moe:\n", quant_formats());
+  return f;
+}
 
 int64_t gguf_gemm_parts(at::Tensor& out, at::Tensor& ws, const at::Tensor& x, const std::vector<at::Tensor>& qs,
                         const std::vector<at::Tensor>& rss, const std::vector<int64_t>& qtypes, const std::vector<int64_t>& rows,
@@ -331,14 +352,14 @@ int64_t gguf_gemm_parts(at::Tensor& out, at::Tensor& ws, const at::Tensor& x, co
   const int S = (nsb + per - 1) / per;
   hipserve::GgufPart P[4];
   for (int i = 0; i < np; ++i) {
-    TORCH_CHECK(qtypes[i] >= 0 && qtypes[i] <= 12, "gguf_gemm_parts: kernel qtype 0-12");
-    const bool fp8 = row_scaled_qt(qtypes[i]);
+    const QuantFormat f = tiled_format(qtypes[i], "gguf_gemm_parts");
+    const bool fp8 = f.row_scaled;
     TORCH_CHECK(!fp8 || (rss[i].scalar_type() == at::kFloat && rss[i].is_contiguous() && rss[i].numel() == rows[i] &&
                          rss[i].device() == x.device()), "FP8 / INT8C parts need an fp32 row scale per row");
     TORCH_CHECK(qs[i].scalar_type() == at::kByte && qs[i].is_contiguous() && qs[i].device() == x.device());
     TORCH_CHECK(cols[i] % 4 == 0 && rows[i] % 16 == 0 && rows[i] > 0 && cols[i] + rows[i] <= Ntot,
                 "parts: 16-row multiples at 4-aligned columns inside Ntot");
-    TORCH_CHECK(qs[i].numel() == rows[i] / 16 * nsb * hipserve::gguf_tiled_chunk_bytes(qtypes[i]),
+    TORCH_CHECK(qs[i].numel() == rows[i] / 16 * nsb * f.chunk_bytes,
                 "part q is not a tiled [N/16, K/256, chunk] tensor of its format");
     P[i] = hipserve::GgufPart{qs[i].data_ptr(), fp8 ? rss[i].data_ptr<float>() : nullptr, (int)qtypes[i],
                               (int)rows[i], (int)cols[i]};
@@ -382,7 +403,7 @@ void x_f16_pairs(at::Tensor& x16, at::Tensor& rsc, const at::Tensor& x) {
   hipserve::launch_x_f16_pairs(x16.data_ptr(), rsc.data_ptr<float>(), x.data_ptr(), x.stride(0), M, K, cur_stream());
 }
 
-// prefill GEMM on the tiled GGUF parts (gguf_mfma.hip qpf_kernel) over x16 / rsc from
+// prefill GEMM on the tiled GGUF parts (gguf_mfma.hip qpg_kernel) over x16 / rsc from
 // x_f16_pairs: epi 0 store at each part's column, 1 residual add (out += x . W^T, in
 // place), 2 / 3 SiLU / GELU GLU of parts 0 (gate) and 1 (up) into out[M, rows]. Returns
 // false when the kernel does not take it.
@@ -406,8 +427,8 @@ bool gguf_prefill(at::Tensor& out, const at::Tensor& x16, const at::Tensor& rsc,
   for (int i = 0; i < np; ++i) {
     TORCH_CHECK(qs[i].scalar_type() == at::kByte && qs[i].is_contiguous() && qs[i].device() == x16.device());
     TORCH_CHECK(rows[i] % 16 == 0 && rows[i] > 0 && cols[i] % 4 == 0, "gguf_prefill: 16-row parts, 4-aligned columns");
-    TORCH_CHECK(qtypes[i] >= 0 && qtypes[i] <= 12 &&  // formats without a prefill body: the launcher returns false
-                    qs[i].numel() == rows[i] / 16 * nsb * hipserve::gguf_tiled_chunk_bytes(qtypes[i]),
+    // (a format without a prefill body is no error: the launcher returns false)
+    TORCH_CHECK(qs[i].numel() == rows[i] / 16 * nsb * tiled_format(qtypes[i], "gguf_prefill").chunk_bytes,
                 "gguf_prefill: part q is not a tiled [N/16, K/256, chunk] tensor of its format");
     P[i] = hipserve::GgufPart{qs[i].data_ptr(), nullptr, (int)qtypes[i], (int)rows[i], (int)cols[i]};
     ncols = std::max(ncols, (long)(cols[i] + rows[i]));
@@ -423,10 +444,7 @@ int64_t qmoe_gemm(at::Tensor& out, at::Tensor& ws, const at::Tensor& x, const at
                   int64_t qtype, int64_t N, int64_t K, const at::Tensor& slots, const at::Tensor& tile_expert,
                   int64_t tile, int64_t gather_k, int64_t splits, bool kmajor, int64_t glu) {
   CHECK_DEV(x); CHECK_BF16(x); CHECK_ROWMAJOR(x);
-  // 0-5, 11, 12: GGUF blocks Q4_0, Q4_1, Q8_0, Q4_K, Q5_K, Q6_K, Q2_K, Q3_K (scales inside the blocks, no rs)
-  TORCH_CHECK((qtype >= 0 && qtype <= 6) || (qtype >= 8 && qtype <= 12),
-              "qmoe_gemm: expert formats GGUF Q4_0 / Q4_1 / Q8_0 / Q4_K / Q5_K / Q6_K / Q2_K / Q3_K, FP8 (per-row scale), "
-              "INT8, INT8C, INT4");
+  const QuantFormat f = tiled_format(qtype, "qmoe_gemm", true);
   TORCH_CHECK(tile == 16 || tile == 32 || tile == 64, "qmoe_gemm: tile 16/32/64");
   TORCH_CHECK(N % 16 == 0 && K % 256 == 0 && x.size(1) >= K && x.stride(0) % 8 == 0, "qmoe_gemm: shapes");
   TORCH_CHECK(slots.scalar_type() == at::kInt && tile_expert.scalar_type() == at::kInt && slots.is_contiguous() &&
@@ -434,9 +452,9 @@ int64_t qmoe_gemm(at::Tensor& out, at::Tensor& ws, const at::Tensor& x, const at
               "qmoe_gemm: int32 slots [tiles * tile] and tile_expert [tiles]");
   TORCH_CHECK(q.scalar_type() == at::kByte && q.is_contiguous() && q.dim() == 2 && q.device() == x.device(),
               "qmoe_gemm: q uint8 [E, expert bytes]");
-  const long per_e = N / 16 * (K / 256) * hipserve::gguf_tiled_chunk_bytes(qtype);
+  const long per_e = N / 16 * (K / 256) * f.chunk_bytes;
   TORCH_CHECK(q.size(1) == per_e, "qmoe_gemm: q rows are not tiled [N/16, K/256, chunk] experts");
-  const bool fp8 = qtype == 6 || qtype == 9;
+  const bool fp8 = f.row_scaled;  // FP8, INT8C: the other expert formats carry their scales in the chunks
   TORCH_CHECK(!fp8 || (rs.scalar_type() == at::kFloat && rs.is_contiguous() && rs.dim() == 2 &&
                        rs.size(0) == q.size(0) && rs.size(1) == N), "qmoe_gemm: FP8 / INT8C experts need rs [E, N] fp32");
   TORCH_CHECK(gather_k > 0 || x.size(0) >= slots.numel(), "qmoe_gemm: slot-indexed x needs a row per slot");
@@ -479,10 +497,11 @@ void gguf_dequant_tiled(at::Tensor& out, const at::Tensor& q, const at::Tensor& 
                 "gguf_dequant_tiled: packed matrices of nrows rows (glu: nrows % 128 == 0)");
     TORCH_CHECK(out.numel() >= N / nrows * ((nrows + 127) / 128 * 128) * K, "gguf_dequant_tiled: packed out size");
   }
-  TORCH_CHECK(qtype >= 0 && qtype <= 12 && q.scalar_type() == at::kByte && q.is_contiguous());
-  TORCH_CHECK(q.numel() == N / 16 * (K / 256) * hipserve::gguf_tiled_chunk_bytes(qtype), "not a tiled tensor");
+  const QuantFormat f = tiled_format(qtype, "gguf_dequant_tiled");
+  TORCH_CHECK(q.scalar_type() == at::kByte && q.is_contiguous());
+  TORCH_CHECK(q.numel() == N / 16 * (K / 256) * f.chunk_bytes, "not a tiled tensor");
   TORCH_CHECK(!kmajor || nrows <= 0 || (nrows % 16 == 0 && N % nrows == 0), "gguf_dequant_tiled: k-major matrices of nrows rows");
-  const bool fp8 = row_scaled_qt(qtype);
+  const bool fp8 = f.row_scaled;
   TORCH_CHECK(!fp8 || (rs.scalar_type() == at::kFloat && rs.numel() == N), "FP8 / INT8C need an fp32 row scale");
   c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
   hipserve::launch_gguf_dequant_tiled(out.data_ptr(), q.data_ptr(), fp8 ? rs.data_ptr<float>() : nullptr,
@@ -1324,6 +1343,7 @@ TORCH_LIBRARY(hipserve, m) {
   m.def("gguf_dequant_tiled(Tensor(a!) out, Tensor q, Tensor rs, int qtype, int N, int K, int pack=0, int nrows=0, bool kmajor=False) -> ()",
         &gguf_dequant_tiled);
   m.def("fp8_untile(Tensor(a!) out, Tensor q, int N, int K) -> ()", &fp8_untile);
+  m.def("quant_formats() -> str", &quant_formats);
   m.def("qmoe_gemm(Tensor(a!) out, Tensor(b!) ws, Tensor x, Tensor q, Tensor rs, int qtype, int N, int K, Tensor slots, Tensor tile_expert, int tile, int gather_k, int splits, bool kmajor=False, int glu=0) -> int", &qmoe_gemm);
   m.def("car_create(int rank, int world, int max_bytes, int nb_large=512) -> int", &car_create);
   m.def("car_handle(int state) -> Tensor", &car_handle);

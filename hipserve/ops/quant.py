@@ -17,6 +17,7 @@ GEMM.
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -36,8 +37,37 @@ INT8C = 1003
 # unsigned nibbles u, per-group f16 scale and integer zero point z in [0, 15]:
 # w = (u - z) * s (gguf_tiles.h INT4)
 INT4 = 1004
-KERNEL_QT = {G.Q4_0: 0, G.Q4_1: 1, G.Q8_0: 2, G.Q4_K: 3, G.Q5_K: 4, G.Q6_K: 5, FP8: 6, FP8B: 7, INT8: 8,
-             INT8C: 9, INT4: 10, G.Q2_K: 11, G.Q3_K: 12}
+# One row per format of the tiled kernels (gguf_mfma.hip): the Python copy of
+# csrc/include/hipserve/quant_formats.h (columns described there; held equal by
+# tests/test_native_lib_cpu.py), plus ``qtype``, the ggml / pseudo type id the loaders use
+Format = namedtuple("Format", "name qtype kqt chunk_bytes sub_shift gguf row_scaled prefill moe")
+FORMATS = (
+    Format("Q4_0", G.Q4_0, 0, 2304, 6, True, False, True, True),
+    Format("Q4_1", G.Q4_1, 1, 2560, 6, True, False, True, True),
+    Format("Q8_0", G.Q8_0, 2, 4352, 2, True, False, True, True),
+    Format("Q4_K", G.Q4_K, 3, 2304, 6, True, False, True, True),
+    Format("Q5_K", G.Q5_K, 4, 2816, 5, True, False, True, True),
+    Format("Q6_K", G.Q6_K, 5, 3360, 4, True, False, True, True),
+    Format("FP8", FP8, 6, 4096, -1, False, True, False, True),
+    Format("FP8B", FP8B, 7, 4224, -1, False, True, False, False),
+    Format("INT8", INT8, 8, 4608, -1, False, False, False, True),
+    Format("INT8C", INT8C, 9, 4096, -1, False, True, False, True),
+    Format("INT4", INT4, 10, 2560, -1, False, False, False, True),
+    Format("Q2_K", G.Q2_K, 11, 1344, 8, True, False, False, True),
+    Format("Q3_K", G.Q3_K, 12, 1824, 7, True, False, False, True),
+)
+BY_KQT = {f.kqt: f for f in FORMATS}  # kernel format id -> row; below: views of the table
+KERNEL_QT = {f.qtype: f.kqt for f in FORMATS}
+CHUNK_BYTES = {f.qtype: f.chunk_bytes for f in FORMATS}
+# gguf_mfma.hip places each quantised integer at bit SUB_SHIFT of a subnormal f16 and scales it
+# by 2^(24 - SUB_SHIFT) inside the f16 FMA: every block scale must stay below 65504 / 2^(24 -
+# SUB_SHIFT) (|w| up to ~2-4). Weights beyond that (none in practice) run on the v1 kernel;
+# Q2_K / Q3_K (limits 0.9995 / 0.4998) have none: QuantWeight.from_gguf keeps such a weight as bf16.
+SUB_SHIFT = {f.qtype: f.sub_shift for f in FORMATS if f.sub_shift >= 0}
+QPG_KQT = tuple(f.kqt for f in FORMATS if f.prefill)  # the block prefill GEMM (qpg_kernel) takes them
+# every GGUF block format: no resident bf16 shadow by default, expert stacks checked
+# against the subnormal-dequant range
+GGUF_KQT = tuple(f.kqt for f in FORMATS if f.gguf)
 MAX_FUSED_M = 64
 # the W8A8 FP8 decode GEMM (fp8_decode.hip) also takes the decode graph buckets above 64
 # rows (up to 256, max_num_seqs' default): one weight stream per step instead of the
@@ -79,10 +109,6 @@ def repack(raw: np.ndarray, qtype: int, N: int, K: int):
         q = b[:, :, 4:20].reshape(N, K // 2)
         return q, d, m, K // 2
     raise NotImplementedError(G.TYPE_NAMES.get(qtype, qtype))
-
-
-CHUNK_BYTES = {G.Q4_K: 2304, G.Q5_K: 2816, G.Q6_K: 3360, G.Q8_0: 4352, G.Q4_0: 2304, G.Q4_1: 2560,
-               FP8: 4096, FP8B: 4224, INT8: 4608, INT8C: 4096, INT4: 2560, G.Q2_K: 1344, G.Q3_K: 1824}
 
 
 def _lanes(a: np.ndarray, n_ld: int) -> np.ndarray:
@@ -133,14 +159,6 @@ def repack_tiled(raw: np.ndarray, qtype: int, N: int, K: int) -> np.ndarray:
     out = np.concatenate(parts, axis=2)
     assert out.shape[2] == CHUNK_BYTES[qtype]
     return np.ascontiguousarray(out)
-
-
-# gguf_mfma.hip places each quantised integer at bit SUB_SHIFT of a subnormal f16 and
-# scales it by 2^(24 - SUB_SHIFT) inside the f16 FMA: every block scale must stay below
-# 65504 / 2^(24 - SUB_SHIFT) (|w| up to ~2-4). Weights beyond that (none in practice)
-# run on the v1 kernel. Q2_K / Q3_K (2- / 3-bit integers: shifts 8 / 7, limits 0.9995 / 0.4998) have
-# no v1 kernel: QuantWeight.from_gguf keeps such a weight as bf16.
-SUB_SHIFT = {G.Q4_K: 6, G.Q5_K: 5, G.Q6_K: 4, G.Q8_0: 2, G.Q4_0: 6, G.Q4_1: 6, G.Q2_K: 8, G.Q3_K: 7}
 
 
 def sub_scale_ok(raw, qtype: int) -> bool:
@@ -711,10 +729,6 @@ def quant_partial(x: torch.Tensor, w: QuantWeight, x16: torch.Tensor | None = No
 QPREFILL_MODE = os.environ.get("HIPSERVE_QPREFILL", "auto")
 QPREFILL = QPREFILL_MODE != "0"
 QPF_CHOICE: dict = {}  # weight signature -> the block kernel was faster at start-up
-QPG_KQT = (0, 1, 2, 3, 4, 5)  # kernel qtypes Q4_0 .. Q6_K: the block prefill GEMM (qpg_kernel) takes them
-# every GGUF block format (+ Q2_K, Q3_K): no resident bf16 shadow by default, expert stacks
-# checked against the subnormal-dequant range
-GGUF_KQT = QPG_KQT + (KERNEL_QT[G.Q2_K], KERNEL_QT[G.Q3_K])
 
 
 def qprefill_ok(w, M: int, glu: bool = False, timed: bool = True) -> bool:
@@ -950,20 +964,19 @@ class QuantMoE:
     """The quantised experts of one MoE projection, stacked for the expert GEMM
     (``qmoe_gemm``, gguf_mfma.hip MoE mode): ``q`` uint8 [E, N/16 * K/256 * chunk]
     (each expert in the v2 tiled layout), row scales ``rs`` [E, N] for FP8 / INT8C (empty
-    for the formats whose scales sit inside the chunks). Formats: INT8 (compressed-tensors
-    8-bit, the reference's AWQ-8bit export), INT4 (AutoAWQ gemm / compressed-tensors 4-bit),
-    per-channel FP8, and the GGUF blocks Q4_0 /
-    Q4_1 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K (``from_blocks``: a MoE GGUF's ``*_exps`` tensors stay
-    resident as their blocks only). Prefill runs bf16 expert GEMMs on ``dense`` (a resident
+    for the formats whose scales sit inside the chunks). Formats (``moe`` in FORMATS): INT8 /
+    INT8C (compressed-tensors 8-bit, the reference's AWQ-8bit export), INT4 (AutoAWQ gemm /
+    compressed-tensors 4-bit), per-channel FP8, and the GGUF blocks (``from_blocks``: a MoE
+    GGUF's ``*_exps`` tensors stay resident as their blocks only). Prefill runs bf16 expert GEMMs on ``dense`` (a resident
     shadow when asked for, else a per-call dequantised scratch)."""
 
-    # GGUF Q4_0 .. Q6_K, Q2_K, Q3_K (scales in the blocks), FP8 (per-row scale), INT8, INT8C (per-row scale), INT4
-    KERNEL_QTS = GGUF_KQT + (6, 8, 9, 10)
+    KERNEL_QTS = tuple(f.kqt for f in FORMATS if f.moe)
 
     def __init__(self, parts: list, kmajor: bool = False):
         p0 = parts[0]
         assert all(p.kqt == p0.kqt and p.N == p0.N and p.K == p0.K and p.tiled for p in parts)
-        rs = torch.stack([p.rs for p in parts]).contiguous() if p0.kqt in (6, 9) else None
+        f = BY_KQT[p0.kqt]
+        rs = torch.stack([p.rs for p in parts]).contiguous() if f.row_scaled and f.moe else None
         self._init(torch.stack([p.q.reshape(-1) for p in parts]).contiguous(), p0.kqt, p0.N, p0.K, rs, kmajor)
 
     def _init(self, q: torch.Tensor, kqt: int, N: int, K: int, rs, kmajor: bool):
@@ -1022,7 +1035,7 @@ class QuantMoE:
         if kqt not in QuantMoE.KERNEL_QTS or N % 16 or K % 256:
             return False
         if raw is not None and kqt in GGUF_KQT:
-            return sub_scale_ok(raw, next(t for t, k in KERNEL_QT.items() if k == kqt))
+            return sub_scale_ok(raw, BY_KQT[kqt].qtype)
         return True
 
 

@@ -875,13 +875,13 @@ def load_gguf_weights(model, path: str):
             lw.q_norm = torch.from_numpy(gf.tensor_f32(p + "attn_q_norm.weight").astype(np.float32)).to(dev)
             lw.k_norm = torch.from_numpy(gf.tensor_f32(p + "attn_k_norm.weight").astype(np.float32)).to(dev)
         model.layers.append(lw)
-    from ..ops.quant import KERNEL_QT, QuantMoE, quant_linear
+    from ..ops.quant import BY_KQT, QuantMoE, quant_linear
 
-    # the Q2_K / Q3_K projections and expert stacks resident as tiled blocks only
-    q23 = (KERNEL_QT[Q2_K], KERNEL_QT[Q3_K])
+    def q23(w):  # a Q2_K / Q3_K projection part or expert stack: resident as tiled blocks only
+        return BY_KQT[w.kqt].qtype in (Q2_K, Q3_K)
     mats = [model.lm_head] + [w for lw in model.layers for w in (lw.wqkv, lw.wo, lw.wgu, lw.wd)]
-    held = [p.nbytes for w in mats if isinstance(w, QuantWeight) for p in w.parts if p.kqt in q23]
-    held += [w.q.numel() for lw in model.layers for w in (lw.w13, lw.w2) if isinstance(w, QuantMoE) and w.kqt in q23]
+    held = [p.nbytes for w in mats if isinstance(w, QuantWeight) for p in w.parts if q23(p)]
+    held += [w.q.numel() for lw in model.layers for w in (lw.w13, lw.w2) if isinstance(w, QuantMoE) and q23(w)]
     if held:
         log.info("GGUF %s: %d Q2_K / Q3_K matrices and expert stacks kept as tiled blocks, %.1f MB", path, len(held),
                  sum(held) / 1e6)

@@ -275,6 +275,8 @@ def load_hf_weights(model: LlamaModel, model_path: str):
     Qwen3-MoE (incl. the fused, transposed expert tensors of Qwen3-VL-MoE), Gemma-3
     text (sandwich norms stored as fp32 ``1 + w``), Phi-3 (fused qkv / gate_up).
     Multimodal wrappers are read through their language-model prefix."""
+    from ..ops import quant as Q
+
     ck = _Ckpt(resolve_checkpoint_dir(model_path))
     cfg, tp = model.cfg, model.tp
     r, W = tp.rank, tp.world_size
@@ -306,16 +308,12 @@ def load_hf_weights(model: LlamaModel, model_path: str):
     def proj(specs):
         """specs: [(name, axis, start, stop)] stacked along the output rows."""
         if native_fp8 and all(ck.is_fp8_e4m3(n) for n, *_ in specs):
-            from ..ops import quant as Q
-
             parts = [ck.fp8_part(n, ax, a, b) for n, ax, a, b in specs]
             if all(pp is not None for pp in parts) and all(
                     pp[0].shape[0] % 16 == 0 and pp[0].shape[1] % 256 == 0 for pp in parts):
                 n_fp8[0] += 1
                 return Q.QuantWeight([Q.QuantPart.from_fp8(qq, sc, dev) for qq, sc in parts])
         if native_fp8 and all(ck.is_int8_ct(n) for n, *_ in specs):
-            from ..ops import quant as Q
-
             parts = [ck.int8_part(n, ax, a, b) for n, ax, a, b in specs]
             if all(pp is not None for pp in parts) and all(
                     pp[0].shape[0] % 16 == 0 and pp[0].shape[1] % 256 == 0
@@ -323,8 +321,6 @@ def load_hf_weights(model: LlamaModel, model_path: str):
                 n_fp8[0] += 1
                 return Q.QuantWeight([Q.QuantPart.from_int8(u, sc, zp, dev) for u, sc, zp in parts])
         if native_int4 and all(ck.is_int4(n) for n, *_ in specs):
-            from ..ops import quant as Q
-
             parts = [ck.int4_part(n, ax, a, b) for n, ax, a, b in specs]
             # a split group, or a shape / group the kernel does not take: bf16 for this projection
             if all(pp is not None for pp in parts) and all(
@@ -396,7 +392,7 @@ def load_hf_weights(model: LlamaModel, model_path: str):
             lw.router, lw.w13, lw.w2 = _load_experts(ck, p, cfg, r, inter, to, dev if native_fp8 else None,
                                                      getattr(model, "moe_shard", None), int4=native_int4)
             for w in (lw.w13, lw.w2):
-                if getattr(w, "kqt", None) == 10:
+                if getattr(w, "kqt", None) == Q.KERNEL_QT[Q.INT4]:
                     n_int4[1] += 1
                     n_int4[2] += w.q.numel()
         elif ck.has(p + "mlp.gate_up_proj.weight"):  # Phi-3: fused [gate; up]
@@ -410,8 +406,6 @@ def load_hf_weights(model: LlamaModel, model_path: str):
             lw.wd = proj([(p + "mlp.down_proj.weight", 1, r * inter, (r + 1) * inter)])
         model.layers.append(lw)
     if n_fp8[0]:
-        from ..ops import quant as Q
-
         model.quant_linear = Q.quant_linear
     if n_int4[0] or n_int4[1]:
         log.info("rank %d/%d: %d projections and %d expert stacks resident as tiled 4-bit chunks only "

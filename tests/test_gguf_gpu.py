@@ -227,7 +227,7 @@ def test_fp8_linear_matches_fp32(mode, M):
         qs.append(q)
         ss.append(s)
     qw = Q.QuantWeight([Q.QuantPart.from_fp8(q, s, "cuda") for q, s in zip(qs, ss)])
-    assert qw.v2 and qw.parts[0].kqt == (7 if mode == "block" else 6)
+    assert qw.v2 and qw.parts[0].kqt == Q.KERNEL_QT[Q.FP8B if mode == "block" else Q.FP8]
     wref = torch.cat([_fp8_ref(q, s, q.shape[0], K) for q, s in zip(qs, ss)]).cuda()
     x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
     want = x.float() @ wref.T
@@ -336,7 +336,7 @@ def test_int8_linear_matches_fp32(group, asym, M):
     scale = torch.rand(N, K // G) * 2e-3 + 1e-4
     zp = torch.randint(-8, 8, (N, K // G)) if asym else None
     qw = Q.QuantWeight([Q.QuantPart.from_int8((q + 128).to(torch.uint8), scale, zp, "cuda")])
-    assert qw.v2 and qw.parts[0].kqt == (9 if group == 0 and not asym else 8)  # per channel: INT8C
+    assert qw.v2 and qw.parts[0].kqt == Q.KERNEL_QT[Q.INT8C if group == 0 and not asym else Q.INT8]  # per channel: INT8C
     wref = ((q - (zp.repeat_interleave(G, 1) if asym else 0)).float() * scale.repeat_interleave(G, 1)).cuda()
     x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
     want = x.float() @ wref.T
@@ -383,7 +383,7 @@ def test_int8_pack_quantized_checkpoint_native(tmp_path):
         mm = eng.runner.model
         assert isinstance(mm.layers[0].wqkv, Q.QuantWeight) == native
         if native:
-            assert mm.layers[0].wqkv.parts[0].kqt == 8
+            assert mm.layers[0].wqkv.parts[0].kqt == Q.KERNEL_QT[Q.INT8]
         orig = mm.compute_logits
 
         def cap(h, orig=orig, native=native):

@@ -53,7 +53,7 @@ def _case(group, asym, wide=False):
 def _check(qw, wref, M, seed):
     from hipserve.ops import quant as Q
 
-    assert qw.parts[0].kqt == 10 and qw.v2
+    assert qw.parts[0].kqt == Q.KERNEL_QT[Q.INT4] and qw.v2
     torch.manual_seed(seed)
     x = torch.randn(M, K, device=DEV, dtype=torch.bfloat16)
     want = x.float() @ wref.T
@@ -165,9 +165,11 @@ def _experts(E):
 def test_int4_expert_gemm_vs_fp32(T, E, k):
     """qmoe_gemm on INT4 experts: w13 super-chunk major with the SiLU-GLU epilogue, then w2,
     against the fp32 routed computation on the dequantised experts."""
+    from hipserve.ops import quant as Q
+
     op = torch.ops.hipserve
     w13, w2, d13, d2 = _experts(E)
-    assert w13.kqt == 10 and w2.kqt == 10 and w13.kmajor and not w2.kmajor
+    assert w13.kqt == w2.kqt == Q.KERNEL_QT[Q.INT4] and w13.kmajor and not w2.kmajor
     H, I = 256, 256
     torch.manual_seed(T + E)
     P = T * k
@@ -270,7 +272,7 @@ def test_int4_checkpoint_native(tmp_path, fmt, group):
     def native(mm):
         for lw in mm.layers:
             for w in (lw.wqkv, lw.wo, lw.wgu, lw.wd):
-                assert isinstance(w, Q.QuantWeight) and all(p.kqt == 10 for p in w.parts)
+                assert isinstance(w, Q.QuantWeight) and all(p.kqt == Q.KERNEL_QT[Q.INT4] for p in w.parts)
         assert not isinstance(mm.lm_head, Q.QuantWeight)  # lm_head and the embeddings stay bf16
 
     def dense(mm):
@@ -370,9 +372,9 @@ def test_int4_expert_checkpoint_native(tmp_path):
 
     def native(mm):
         for lw in mm.layers:
-            assert isinstance(lw.w13, Q.QuantMoE) and lw.w13.kqt == 10 and lw.w13.kmajor
-            assert isinstance(lw.w2, Q.QuantMoE) and lw.w2.kqt == 10
-            assert isinstance(lw.wqkv, Q.QuantWeight) and lw.wqkv.parts[0].kqt == 10
+            assert isinstance(lw.w13, Q.QuantMoE) and lw.w13.kqt == Q.KERNEL_QT[Q.INT4] and lw.w13.kmajor
+            assert isinstance(lw.w2, Q.QuantMoE) and lw.w2.kqt == Q.KERNEL_QT[Q.INT4]
+            assert isinstance(lw.wqkv, Q.QuantWeight) and lw.wqkv.parts[0].kqt == Q.KERNEL_QT[Q.INT4]
 
     def dense(mm):
         lw = mm.layers[0]
@@ -405,7 +407,7 @@ def test_int4_engine_graph_equals_eager():
                         tp=TPGroup(0, 1, None, torch.device("cuda", 0)))
         lw = eng.runner.model.layers[0]
         for w in (lw.wqkv, lw.wo, lw.wgu, lw.wd):
-            assert isinstance(w, Q.QuantWeight) and all(p.kqt == 10 for p in w.parts)
+            assert isinstance(w, Q.QuantWeight) and all(p.kqt == Q.KERNEL_QT[Q.INT4] for p in w.parts)
         assert eng.runner.use_graphs != eager
         res = eng.generate(prompts, sp)
         assert all(len(r[0]) == 16 for r in res)

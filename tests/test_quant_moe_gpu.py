@@ -254,7 +254,7 @@ def test_qmoe_glu_epilogue_and_kmajor_bit_exact(kind, T, E, k):
             q = torch.round(wf / s.repeat_interleave(G, 1)).clamp(-127, 127)
             parts.append(Q.QuantPart.from_int8((q + 128).to(torch.uint8), s, None, DEV))
     w = Q.QuantMoE(parts)
-    assert w.kqt == {"fp8": 6, "int8": 9, "int8g": 8}[kind]
+    assert w.kqt == Q.KERNEL_QT[{"fp8": Q.FP8, "int8": Q.INT8C, "int8g": Q.INT8}[kind]]
     P = T * k
     tile = 16 if P <= 8 * E else 32
     cap = -(-(P + E * (tile - 1)) // tile) * tile
