@@ -65,13 +65,19 @@ size_t sample_workspace_floats(int rows, int V);
 void launch_sample(long* out_tok, float* out_lp, const void* logits, bool is_bf16,
                    long stride, int rows, int V, const float* temperature,
                    const int* top_k, const float* top_p, const long* seeds,
-                   const long* steps, float* ws, hipStream_t s, bool two_rounds = true);
+                   const long* steps, float* ws, hipStream_t s, bool two_rounds = true,
+                   const float* min_p = nullptr);  // per row, nullptr or <= 0: off
 
 // penalties.hip — device-side OpenAI penalties + top-n logprobs (graph-capturable).
 // counts int32 [slots, V], seen bits [slots, ceil(V/32)]; slot < 0: row untouched.
 void launch_penalty_apply(void* logits, bool is_bf16, long stride, int rows, int V, const int* slot,
                           const float* pres, const float* freq, const float* rep, const int* counts,
                           const unsigned int* seen, hipStream_t s);
+// logit_bias: row r with slot[r] = s >= 0 gets logits[r][ids[s][e]] += vals[s][e], e < n[s]
+// (ids / vals [nslots, width], ids unique within a slot; ids outside [0, V) are skipped)
+void launch_logit_bias_apply(void* logits, bool is_bf16, long stride, int rows, int V, const int* slot,
+                             const int* ids, const float* vals, const int* n, int nslots, int width,
+                             hipStream_t s);
 void launch_penalty_update(const long* tok, const int* slot, int n, int* counts, unsigned int* seen, int V,
                            hipStream_t s);
 void launch_penalty_init(int* counts, unsigned int* seen, int V, const int* slots, const int* off,

@@ -10,6 +10,9 @@
 // (l > 0 ? l / r : l * r), then l -= frequency * count + presence * (count > 0).
 //   penalty_init    (re)build a slot from prompt + already generated ids (the
 //                   step that samples a sequence's first token, or a recompute)
+//   logit_bias_apply  OpenAI logit_bias from its own per-sequence slot table (ids, biases,
+//                   count), added to the logits in place BEFORE the penalties (vLLM's
+//                   order) and after top_logprobs
 //   penalty_apply   logits rows in place, rows with slot < 0 untouched
 //   penalty_update  count the tokens sampled this step (after the sampler)
 //   top_logprobs    per row with n > 0: n largest log-softmax entries (radix
@@ -60,6 +63,32 @@ __global__ __launch_bounds__(256) void penalty_apply_kernel(T* __restrict__ logi
     const int c = cnt[v];
     l -= fp * (float)c + (c > 0 ? pp : 0.f);
     st_logit(row, v, l);
+  }
+}
+
+// OpenAI logit_bias: one workgroup per logits row; thread e of a row with slot s adds
+// vals[s][e] to logit ids[s][e] (fp32 add, stored back in the logits' dtype). Ids are
+// unique within a slot (request validation), so no two threads touch one logit; an id
+// outside [0, V) is skipped, so a bad table never writes out of bounds.
+constexpr int kBiasThreads = 320;
+
+template <typename T>
+__global__ __launch_bounds__(kBiasThreads) void logit_bias_apply_kernel(T* __restrict__ logits, long stride, int V,
+                                                                        const int* __restrict__ slot,
+                                                                        const int* __restrict__ ids,
+                                                                        const float* __restrict__ vals,
+                                                                        const int* __restrict__ n, int nslots,
+                                                                        int width) {
+  const int r = blockIdx.x;
+  const int s = slot[r];
+  if (s < 0 || s >= nslots) return;
+  const int cnt = min(n[s], width);
+  if (cnt <= 0) return;
+  T* row = logits + (long)r * stride;
+  for (int e = threadIdx.x; e < cnt; e += kBiasThreads) {
+    const int id = ids[(long)s * width + e];
+    if (id < 0 || id >= V) continue;
+    st_logit(row, id, ld_logit(row, id) + vals[(long)s * width + e]);
   }
 }
 
@@ -239,6 +268,18 @@ void launch_penalty_apply(void* logits, bool is_bf16, long stride, int rows, int
   else
     penalty_apply_kernel<float><<<grid, 256, 0, s>>>(static_cast<float*>(logits), stride, V, slot, pres, freq, rep,
                                                      counts, seen, words);
+}
+
+void launch_logit_bias_apply(void* logits, bool is_bf16, long stride, int rows, int V, const int* slot,
+                             const int* ids, const float* vals, const int* n, int nslots, int width,
+                             hipStream_t s) {
+  if (rows <= 0 || nslots <= 0 || width <= 0) return;
+  if (is_bf16)
+    logit_bias_apply_kernel<unsigned short><<<rows, kBiasThreads, 0, s>>>(static_cast<unsigned short*>(logits),
+                                                                          stride, V, slot, ids, vals, n, nslots, width);
+  else
+    logit_bias_apply_kernel<float><<<rows, kBiasThreads, 0, s>>>(static_cast<float*>(logits), stride, V, slot, ids,
+                                                                 vals, n, nslots, width);
 }
 
 void launch_penalty_update(const long* tok, const int* slot, int n, int* counts, unsigned int* seen, int V,

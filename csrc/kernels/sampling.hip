@@ -11,7 +11,9 @@
 //           serialise a histogram)
 //   sample  Gumbel-max race among survivors: argmax (x-m)/T - log(-log u_i),
 //           u_i = hash(row_key(seed, step), i) — an exact draw from the filtered
-//           softmax; elements that provably cannot win skip the hash
+//           softmax; elements that provably cannot win skip the hash, and so do
+//           those under a row's min_p cut (p_i < min_p * p_max), which applies
+//           after top-k / top-p and does not move their thresholds
 #include "hipserve/common.h"
 #include "hipserve/kernels.h"
 
@@ -44,6 +46,25 @@ HS_DEVICE float uniform01(unsigned int key, unsigned int i) {
   h ^= h >> 13; h *= 0xC2B2AE35u;
   h ^= h >> 16;
   return ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
+}
+
+// max Gumbel noise for 24-bit u is 17.33 and the argmax token scores >= -2.85:
+// an element whose scaled logit is below -20.3 can never win -> no hash needed.
+constexpr float kNoWin = -20.3f;
+
+// Lowest scaled logit z = (x - rowmax) / T that enters the Gumbel race: the no-win
+// bound, raised to ln(min_p) for a row with min_p > 0 (a token survives iff
+// p_i >= min_p * p_max, i.e. z >= ln(min_p)). The cut is clamped to <= 0 so the row
+// maximum (z = 0) survives whatever rounding does to the logarithm. A null pointer,
+// min_p <= 0 or NaN leave the bound alone: the draw is then bit-identical to a
+// sampler without min_p. The value is wave-uniform and is moved to a scalar register
+// (the logarithm leaves it in a vector one), so the Gumbel pass holds no more
+// vector registers per lane than with the constant bound.
+HS_DEVICE float gumbel_cut(float no_win, const float* __restrict__ min_p, int row) {
+  if (min_p == nullptr) return no_win;
+  const float mp = min_p[row];
+  const float cut = mp > 0.f ? fmaxf(no_win, fminf(__logf(mp), 0.f)) : no_win;
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cut)));
 }
 
 // Make the register-resident row opaque between passes so the compiler does not
@@ -93,7 +114,7 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(
     const T* __restrict__ logits, long stride, int V,
     const float* __restrict__ temperature, const int* __restrict__ top_k,
     const float* __restrict__ top_p, const long* __restrict__ seeds,
-    const long* __restrict__ steps) {
+    const long* __restrict__ steps, const float* __restrict__ min_p) {
   // Elements [0, R) live in registers (NV 16-byte chunks per lane), the rest of
   // the row [R, V) in LDS (dynamic shared memory, 16-byte chunks).
   constexpr int R = kSampThreads * NV * 8;
@@ -179,6 +200,9 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(
     return;
   }
   const float inv_t = 1.f / temp;
+  // the Gumbel pass's cut, taken here as one scalar: computed next to that pass it
+  // cost the NV = 8 body 18 more spilled vector registers
+  const float zcut = gumbel_cut(kNoWin, min_p, row);
   const int k = top_k[row];
   const float p = top_p[row];
   unsigned int floor_key = 0;  // survivors: key16 >= floor_key
@@ -237,15 +261,12 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(
 
   // ---- Gumbel-max among survivors
   const unsigned int rkey = row_key((unsigned long long)seeds[row], (unsigned long long)steps[row]);
-  // max Gumbel noise for 24-bit u is 17.33 and the argmax token scores >= -2.85:
-  // an element whose scaled logit is below -20.3 can never win -> no hash needed.
-  constexpr float kNoWin = -20.3f;
   float best = -INFINITY;
   int bi = ramax;
   visit([&](int idx, unsigned short b) {
     if (idx >= V || key16(b) < floor_key) return;
     const float z = (bf16_to_f32(b) - rmax) * inv_t;
-    if (z < kNoWin) return;
+    if (z < zcut) return;
     const float u = uniform01(rkey, (unsigned int)idx);
     const float g = z - __logf(-__logf(u));
     if (g > best) { best = g; bi = idx; }
@@ -278,9 +299,9 @@ constexpr size_t kSampLdsBudget = 142 * 1024;  // dynamic LDS for the row tail
 template <typename T>
 static void launch_sample_t(long* out_tok, float* out_lp, const T* logits, long stride, int rows,
                             int V, const float* temperature, const int* top_k, const float* top_p,
-                            const long* seeds, const long* steps, hipStream_t s) {
+                            const long* seeds, const long* steps, const float* min_p, hipStream_t s) {
   if (V <= kSampThreads * 32) {
-    sample_kernel<4, T><<<rows, kSampThreads, 0, s>>>(out_tok, out_lp, logits, stride, V, temperature, top_k, top_p, seeds, steps);
+    sample_kernel<4, T><<<rows, kSampThreads, 0, s>>>(out_tok, out_lp, logits, stride, V, temperature, top_k, top_p, seeds, steps, min_p);
     return;
   }
   constexpr int R = kSampThreads * 7 * 8;
@@ -289,7 +310,7 @@ static void launch_sample_t(long* out_tok, float* out_lp, const T* logits, long 
     fprintf(stderr, "hipserve sample: vocab %d exceeds the register+LDS row budget\n", V);
     abort();
   }
-  sample_kernel<8, T><<<rows, kSampThreads, lds, s>>>(out_tok, out_lp, logits, stride, V, temperature, top_k, top_p, seeds, steps);
+  sample_kernel<8, T><<<rows, kSampThreads, lds, s>>>(out_tok, out_lp, logits, stride, V, temperature, top_k, top_p, seeds, steps, min_p);
 }
 
 // ============================================================================
@@ -743,7 +764,8 @@ __global__ __launch_bounds__(256) void mc_thresh_kernel(const int* __restrict__ 
 template <typename T>
 __global__ __launch_bounds__(kMcThreads) void mc_gumbel_kernel(const T* __restrict__ logits, long stride, int V,
                                                               const long* __restrict__ seeds,
-                                                              const long* __restrict__ steps, float* __restrict__ ws,
+                                                              const long* __restrict__ steps,
+                                                              const float* __restrict__ min_p, float* __restrict__ ws,
                                                               int C) {
   const int chunk = blockIdx.x, row = blockIdx.y;
   const McLayout L{C};
@@ -757,7 +779,7 @@ __global__ __launch_bounds__(kMcThreads) void mc_gumbel_kernel(const T* __restri
   const float M = st[ST_M], inv_t = st[ST_INVT];
   const unsigned int floor_key = (unsigned int)st[ST_FLOOR];
   const unsigned int rkey = row_key((unsigned long long)seeds[row], (unsigned long long)steps[row]);
-  constexpr float kNoWin = -20.3f;
+  const float zcut = gumbel_cut(kNoWin, min_p, row);
   float best = -INFINITY;
   int bi = 0x7fffffff;
 #pragma unroll
@@ -767,7 +789,7 @@ __global__ __launch_bounds__(kMcThreads) void mc_gumbel_kernel(const T* __restri
       const int idx = mc_idx(chunk, j, e);
       if (idx >= V || key16(d[j][e]) < floor_key) continue;
       const float z = (bf16_to_f32(d[j][e]) - M) * inv_t;
-      if (z < kNoWin) continue;
+      if (z < zcut) continue;
       const float u = uniform01(rkey, (unsigned int)idx);
       const float g = z - __logf(-__logf(u));
       if (g > best || (g == best && idx < bi)) { best = g; bi = idx; }
@@ -824,7 +846,7 @@ size_t sample_workspace_floats(int rows, int V) {
 template <typename T>
 static void launch_sample_mc(long* out_tok, float* out_lp, const T* logits, long stride, int rows, int V,
                              const float* temperature, const int* top_k, const float* top_p, const long* seeds,
-                             const long* steps, float* ws, bool two_rounds, hipStream_t s) {
+                             const long* steps, const float* min_p, float* ws, bool two_rounds, hipStream_t s) {
   const int C = (V + kMcChunk - 1) / kMcChunk;
   const dim3 cg(C, rows);
   mc_stats_kernel<T><<<cg, kMcThreads, 0, s>>>(logits, stride, V, temperature, top_k, top_p, ws, C);
@@ -835,28 +857,28 @@ static void launch_sample_mc(long* out_tok, float* out_lp, const T* logits, long
     mc_fine_kernel<T><<<cg, kMcThreads, 0, s>>>(logits, stride, V, ws, C, 1);
     mc_thresh_kernel<<<rows, 256, 0, s>>>(top_k, top_p, V, ws, C, 1);
   }
-  mc_gumbel_kernel<T><<<cg, kMcThreads, 0, s>>>(logits, stride, V, seeds, steps, ws, C);
+  mc_gumbel_kernel<T><<<cg, kMcThreads, 0, s>>>(logits, stride, V, seeds, steps, min_p, ws, C);
   mc_final_kernel<T><<<rows, 64, 0, s>>>(out_tok, out_lp, logits, stride, V, ws, C);
 }
 
 void launch_sample(long* out_tok, float* out_lp, const void* logits, bool is_bf16,
                    long stride, int rows, int V, const float* temperature,
                    const int* top_k, const float* top_p, const long* seeds,
-                   const long* steps, float* ws, hipStream_t s, bool two_rounds) {
+                   const long* steps, float* ws, hipStream_t s, bool two_rounds, const float* min_p) {
   if (rows <= 0) return;
   if (ws != nullptr && V >= kMcMinVocab) {
     if (is_bf16)
       launch_sample_mc(out_tok, out_lp, static_cast<const unsigned short*>(logits), stride, rows, V, temperature,
-                       top_k, top_p, seeds, steps, ws, two_rounds, s);
+                       top_k, top_p, seeds, steps, min_p, ws, two_rounds, s);
     else
       launch_sample_mc(out_tok, out_lp, static_cast<const float*>(logits), stride, rows, V, temperature, top_k,
-                       top_p, seeds, steps, ws, two_rounds, s);
+                       top_p, seeds, steps, min_p, ws, two_rounds, s);
     return;
   }
   if (is_bf16)
-    launch_sample_t(out_tok, out_lp, static_cast<const unsigned short*>(logits), stride, rows, V, temperature, top_k, top_p, seeds, steps, s);
+    launch_sample_t(out_tok, out_lp, static_cast<const unsigned short*>(logits), stride, rows, V, temperature, top_k, top_p, seeds, steps, min_p, s);
   else
-    launch_sample_t(out_tok, out_lp, static_cast<const float*>(logits), stride, rows, V, temperature, top_k, top_p, seeds, steps, s);
+    launch_sample_t(out_tok, out_lp, static_cast<const float*>(logits), stride, rows, V, temperature, top_k, top_p, seeds, steps, min_p, s);
 }
 
 }  // namespace hipserve

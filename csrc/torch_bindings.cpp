@@ -264,7 +264,8 @@ void gelu_and_mul(at::Tensor& out, const at::Tensor& x) {
 
 void sample(at::Tensor& out_tok, at::Tensor& out_lp, const at::Tensor& logits,
             const at::Tensor& temperature, const at::Tensor& top_k, const at::Tensor& top_p,
-            const at::Tensor& seeds, const at::Tensor& steps, bool two_rounds) {
+            const at::Tensor& seeds, const at::Tensor& steps, bool two_rounds,
+            const c10::optional<at::Tensor>& min_p) {
   CHECK_DEV(logits); CHECK_ROWMAJOR(logits);
   TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat);
   TORCH_CHECK(out_tok.scalar_type() == at::kLong && out_lp.scalar_type() == at::kFloat);
@@ -274,6 +275,12 @@ void sample(at::Tensor& out_tok, at::Tensor& out_lp, const at::Tensor& logits,
   const int rows = logits.size(0);
   TORCH_CHECK(out_tok.numel() >= rows && temperature.numel() >= rows && top_k.numel() >= rows &&
               top_p.numel() >= rows && seeds.numel() >= rows && steps.numel() >= rows);
+  const float* minp = nullptr;
+  if (min_p.has_value() && min_p->defined()) {
+    CHECK_DEV((*min_p)); CHECK_CONTIG((*min_p));
+    TORCH_CHECK(min_p->scalar_type() == at::kFloat && min_p->numel() >= rows, "sample: min_p is float [rows]");
+    minp = min_p->data_ptr<float>();
+  }
   c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
   // multi-CU sampler workspace (caching allocator: graph-capturable)
   const size_t wsn = hipserve::sample_workspace_floats(rows, logits.size(1));
@@ -284,7 +291,7 @@ void sample(at::Tensor& out_tok, at::Tensor& out_lp, const at::Tensor& logits,
                           logits.stride(0), rows, logits.size(1), temperature.data_ptr<float>(),
                           top_k.data_ptr<int>(), top_p.data_ptr<float>(), seeds.data_ptr<int64_t>(),
                           steps.data_ptr<int64_t>(), wsn ? ws.data_ptr<float>() : nullptr, cur_stream(),
-                          two_rounds);
+                          two_rounds, minp);
 }
 
 void gguf_gemm(at::Tensor& out, const at::Tensor& x, const at::Tensor& q, const at::Tensor& d,
@@ -656,6 +663,22 @@ void penalty_apply(at::Tensor& logits, const at::Tensor& slot, const at::Tensor&
                                  slot.data_ptr<int>(), pres.data_ptr<float>(), freq.data_ptr<float>(),
                                  rep.data_ptr<float>(), counts.data_ptr<int>(),
                                  reinterpret_cast<const unsigned int*>(seen.data_ptr<int>()), cur_stream());
+}
+
+void logit_bias_apply(at::Tensor& logits, const at::Tensor& slot, const at::Tensor& ids, const at::Tensor& vals,
+                      const at::Tensor& n) {
+  CHECK_DEV(logits); CHECK_ROWMAJOR(logits); CHECK_DEV(slot); CHECK_DEV(ids); CHECK_DEV(vals); CHECK_DEV(n);
+  TORCH_CHECK(logits.dim() == 2 && (logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat));
+  const int rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(slot.scalar_type() == at::kInt && slot.numel() >= rows && slot.is_contiguous());
+  CHECK_CONTIG(ids); CHECK_CONTIG(vals); CHECK_CONTIG(n);
+  TORCH_CHECK(ids.scalar_type() == at::kInt && ids.dim() == 2, "logit_bias ids: int32 [slots, width]");
+  TORCH_CHECK(vals.scalar_type() == at::kFloat && vals.sizes() == ids.sizes(), "logit_bias vals: float [slots, width]");
+  TORCH_CHECK(n.scalar_type() == at::kInt && n.numel() == ids.size(0), "logit_bias n: int32 [slots]");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  hipserve::launch_logit_bias_apply(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, logits.stride(0), rows, V,
+                                    slot.data_ptr<int>(), ids.data_ptr<int>(), vals.data_ptr<float>(),
+                                    n.data_ptr<int>(), ids.size(0), ids.size(1), cur_stream());
 }
 
 void penalty_update(const at::Tensor& tok, const at::Tensor& slot, at::Tensor& counts, at::Tensor& seen) {
@@ -1375,13 +1398,14 @@ TORCH_LIBRARY(hipserve, m) {
   m.def("splitk_rope_cache(Tensor(a!) qkv, Tensor ws, int splits, Tensor positions, Tensor slots, Tensor cos_sin, Tensor(b!) k_cache, Tensor(c!) v_cache, int nq, int nkv, int head_dim, int mode, Tensor? bias=None, Tensor? q_w=None, Tensor? k_w=None, float eps=1e-6) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, int rt, int kw) -> ()");
   m.def("penalty_apply(Tensor(a!) logits, Tensor slot, Tensor pres, Tensor freq, Tensor rep, Tensor counts, Tensor seen) -> ()");
+  m.def("logit_bias_apply(Tensor(a!) logits, Tensor slot, Tensor ids, Tensor vals, Tensor n) -> ()");
   m.def("penalty_update(Tensor tok, Tensor slot, Tensor(a!) counts, Tensor(b!) seen) -> ()");
   m.def("penalty_init(Tensor(a!) counts, Tensor(b!) seen, Tensor slots, Tensor off, Tensor n_prompt, Tensor toks) -> ()");
   m.def("top_logprobs(Tensor logits, Tensor nreq, Tensor(a!) out_ids, Tensor(b!) out_lp) -> ()");
   m.def("layernorm(Tensor(a!) out, Tensor x, Tensor w, Tensor b, Tensor(b!)? residual, float eps) -> ()");
   m.def("gelu_(Tensor(a!) x, bool tanh_approx) -> ()");
   m.def("vision_attention(Tensor(a!) out, Tensor(b!) qkv, Tensor cos_sin, Tensor cu, Tensor tiles, int nh, int D, float scale) -> ()");
-  m.def("sample(Tensor(a!) out_tok, Tensor(b!) out_lp, Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds, Tensor steps, bool two_rounds=True) -> ()");
+  m.def("sample(Tensor(a!) out_tok, Tensor(b!) out_lp, Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds, Tensor steps, bool two_rounds=True, Tensor? min_p=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(hipserve, CUDA, m) {
@@ -1399,6 +1423,7 @@ TORCH_LIBRARY_IMPL(hipserve, CUDA, m) {
   m.impl("prefill_attention", &prefill_attention);
   m.impl("sample", &sample);
   m.impl("penalty_apply", &penalty_apply);
+  m.impl("logit_bias_apply", &logit_bias_apply);
   m.impl("penalty_update", &penalty_update);
   m.impl("penalty_init", &penalty_init);
   m.impl("top_logprobs", &top_logprobs);

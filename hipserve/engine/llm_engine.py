@@ -95,6 +95,7 @@ class LLMEngine:
         V = self.model_cfg.vocab_size
         if any(t < 0 or t >= V for t in ids):
             raise ValueError(f"prompt token id out of range [0, {V})")
+        params.check_vocab(V)
         if len(ids) >= self.max_model_len:
             raise ValueError(f"prompt has {len(ids)} tokens; max_model_len is {self.max_model_len}")
         seq = Sequence(request_id, ids, params, eos_token_ids=self.eos_ids)

@@ -25,6 +25,7 @@ from ..models.llama import AttnMeta, LlamaModel
 from ..ops import get_ops
 from ..parallel.comm import TPGroup
 from ..runtime import native
+from .request import MAX_LOGIT_BIAS
 from .scheduler import SchedulerOutput
 
 log = logging.getLogger("hipserve.runner")
@@ -62,6 +63,10 @@ class StepInputs:
     # tokens that is this row's input id (-1: use ids[row]); consumed on the device
     src: np.ndarray | None = None
     extra: dict = field(default_factory=dict)
+    # min_p / logit_bias, applied on the device (sampling.hip, penalties.hip)
+    min_p: np.ndarray | None = None       # float32 [n]: min_p per sampled row (0: off); None: all off
+    bias_slot: np.ndarray | None = None   # int32 [n]: logit_bias slot per sampled row (-1: none)
+    bias_init: tuple | None = None        # (slots, off, ids, vals): bias slots filled this step
 
 
 def pad_table(times: dict, tol: float = 1.03) -> dict:
@@ -218,6 +223,12 @@ class ModelRunner:
         self.pen_counts = torch.zeros(nslots, V, dtype=torch.int32, device=self.device)
         self.pen_seen = torch.zeros(nslots, (V + 31) // 32, dtype=torch.int32, device=self.device)
         self._free_pen = list(range(nslots - 1, -1, -1))
+        # device logit_bias state, same slot lifecycle: ids, biases and the entry count
+        # of each sequence's OpenAI logit_bias (512 slots x 300 entries: 1.2 MB)
+        self.bias_ids = torch.zeros(nslots, MAX_LOGIT_BIAS, dtype=torch.int32, device=self.device)
+        self.bias_vals = torch.zeros(nslots, MAX_LOGIT_BIAS, dtype=torch.float32, device=self.device)
+        self.bias_n = torch.zeros(nslots, dtype=torch.int32, device=self.device)
+        self._free_bias = list(range(nslots - 1, -1, -1))
         self.init_times["pad_probe_s"] = round(time.time() - t1, 2)
         t1 = time.time()
         self.num_blocks = self._num_kv_blocks()
@@ -473,11 +484,23 @@ class ModelRunner:
         seeds = np.empty(n, np.int64)
         steps = np.empty(n, np.int64)
         pen_slot = pen_vals = nlp = pen_init = None
+        minp = bias_slot = bias_init = None   # stay None on a step where no row uses them
         topn = 0
-        init = []
+        init, binit = [], []
         for i, q in enumerate(sample_seqs):
             p = q.params
             temp[i] = p.temperature
+            if p.min_p:
+                if minp is None:
+                    minp = np.zeros(n, np.float32)
+                minp[i] = p.min_p
+            if p.logit_bias:
+                if bias_slot is None:
+                    bias_slot = np.full(n, -1, np.int32)
+                if q.bias_slot is None:  # first sample (or after a preemption): fill a slot
+                    q.bias_slot = self._free_bias.pop()
+                    binit.append(q)
+                bias_slot[i] = q.bias_slot
             topk[i] = p.top_k if p.top_k > 0 else 0
             topp[i] = p.top_p
             seeds[i] = q.seed
@@ -505,9 +528,16 @@ class ModelRunner:
             pen_init = (np.array([q.pen_slot for q in init], np.int32), off,
                         np.array([q.num_prompt_tokens for q in init], np.int32),
                         np.fromiter((t for x in ids_l for t in x), np.int32, int(off[-1])))
+        if binit:
+            off = np.zeros(len(binit) + 1, np.int32)
+            off[1:] = np.cumsum([len(q.params.logit_bias) for q in binit])
+            bias_init = (np.array([q.bias_slot for q in binit], np.int32), off,
+                         np.fromiter((t for q in binit for t, _ in q.params.logit_bias), np.int32, int(off[-1])),
+                         np.fromiter((b for q in binit for _, b in q.params.logit_bias), np.float32, int(off[-1])))
         inp = StepInputs(ids, pos, slots, Tp, len(so.decode), bt_p, cu_q, ctx_p, tiles, bt_d, ctx_d,
                          np.array(rows, dtype=np.int64), temp, topk, topp, seeds, steps,
-                         pen_slot, pen_vals, nlp, pen_init, topn)
+                         pen_slot, pen_vals, nlp, pen_init, topn,
+                         min_p=minp, bias_slot=bias_slot, bias_init=bias_init)
         if any(s.seq.mm is not None for s in seqs):
             self._prepare_mm(seqs, inp)
         return inp
@@ -550,10 +580,25 @@ class ModelRunner:
                 "images": images}
 
     def release(self, seq):
-        """A finished / aborted sequence gives its penalty slot back."""
+        """A finished / aborted / preempted sequence gives its penalty and logit_bias
+        slots back."""
         if seq.pen_slot is not None:
             self._free_pen.append(seq.pen_slot)
             seq.pen_slot = None
+        if seq.bias_slot is not None:
+            self._free_bias.append(seq.bias_slot)
+            seq.bias_slot = None
+
+    def _fill_bias_slots(self, bias_init):
+        """Copy this step's new logit_bias tables into their slots' rows (every TP rank
+        fills its own copy from the broadcast StepInputs)."""
+        slots, off, ids, vals = bias_init
+        cnt = np.diff(off).astype(np.int32)
+        for j, s in enumerate(slots):
+            a, b = int(off[j]), int(off[j + 1])
+            self.bias_ids[s, :b - a].copy_(torch.from_numpy(ids[a:b]))
+            self.bias_vals[s, :b - a].copy_(torch.from_numpy(vals[a:b]))
+            self.bias_n[s:s + 1].copy_(torch.from_numpy(cnt[j:j + 1]))
 
     # ------------------------------------------------------------ execution
     def _t(self, a, dtype=None):
@@ -571,7 +616,7 @@ class ModelRunner:
     def graph_eligible(self, inp: StepInputs) -> bool:
         # penalties and logprobs run inside the graph (device state + per-row inputs)
         return (self.use_graphs and inp.num_prefill_tokens == 0 and inp.pen_init is None
-                and 0 < inp.num_decode <= self.buckets[-1])
+                and inp.bias_init is None and 0 < inp.num_decode <= self.buckets[-1])
 
     @torch.inference_mode()
     def execute(self, inp: StepInputs):
@@ -605,6 +650,10 @@ class ModelRunner:
             ti = torch.empty(n, TOP_LOGPROBS, dtype=torch.int32, device=self.device)
             tl = torch.empty(n, TOP_LOGPROBS, dtype=torch.float32, device=self.device)
             self.ops.top_logprobs(logits, self._t(inp.nlogprobs), ti, tl)
+        if inp.bias_init is not None:
+            self._fill_bias_slots(inp.bias_init)
+        if inp.bias_slot is not None:  # before the penalties (vLLM's order)
+            self.ops.logit_bias_apply(logits, self._t(inp.bias_slot), self.bias_ids, self.bias_vals, self.bias_n)
         pslot = None
         if inp.pen_slot is not None:
             if inp.pen_init is not None:
@@ -615,7 +664,7 @@ class ModelRunner:
         tok = torch.empty(n, dtype=torch.long, device=self.device)
         lp = torch.empty(n, dtype=torch.float32, device=self.device)
         self.ops.sample(tok, lp, logits, self._t(inp.temperature), self._t(inp.top_k),
-                        self._t(inp.top_p), self._t(inp.seeds), self._t(inp.steps))
+                        self._t(inp.top_p), self._t(inp.seeds), self._t(inp.steps), min_p=self._t(inp.min_p))
         if pslot is not None:
             self.ops.penalty_update(tok, pslot, self.pen_counts, self.pen_seen)
         if inp.top_logprobs:
@@ -668,10 +717,10 @@ class ModelRunner:
     # ------------------------------------------------------------ hipGraphs
     def _graph_forward(self, b: int, full: bool = True):
         """The captured decode step. The lean variant (``full=False``) leaves out the
-        OpenAI penalty and top-n logprob kernels and the sampler's second threshold
-        round (needed only by rows that combine top-k with top-p); a step whose rows
-        need none of them replays it: five launches fewer, ~35 us of a ~5.4 ms
-        Llama-3-8B step."""
+        OpenAI logit_bias, penalty and top-n logprob kernels and the sampler's second
+        threshold round (needed only by rows that combine top-k with top-p); a step
+        whose rows need none of them replays it: six launches fewer, ~35 us of a
+        ~5.4 ms Llama-3-8B step. min_p is a per-row input of the sampler in both."""
         st = self._static
         meta = AttnMeta(num_prefill_tokens=0, num_decode=b, positions=st["pos"][:b],
                         slot_mapping=st["slots"][:b], bt_decode=st["bt"][:b], ctx_decode=st["ctx"][:b],
@@ -685,10 +734,11 @@ class ModelRunner:
         # log-probs of the raw (pre-penalty) distribution, as vLLM's default mode
         if full:
             self.ops.top_logprobs(logits, st["nlp"][:b], st["top_ids"][:b], st["top_lp"][:b])
+            self.ops.logit_bias_apply(logits, st["bslot"][:b], self.bias_ids, self.bias_vals, self.bias_n)
             self.ops.penalty_apply(logits, st["pslot"][:b], st["pres"][:b], st["freq"][:b], st["rep"][:b],
                                    self.pen_counts, self.pen_seen)
         self.ops.sample(st["tok"][:b], st["lp"][:b], logits, st["temp"][:b], st["topk"][:b],
-                        st["topp"][:b], st["seeds"][:b], st["steps"][:b], two_rounds=full)
+                        st["topp"][:b], st["seeds"][:b], st["steps"][:b], two_rounds=full, min_p=st["minp"][:b])
         if full:
             self.ops.penalty_update(st["tok"][:b], st["pslot"][:b], self.pen_counts, self.pen_seen)
 
@@ -715,20 +765,22 @@ class ModelRunner:
         for _ in range(2):
             self._stage.append({
                 "h64": torch.zeros(6 * mb, dtype=torch.long).pin_memory(),
-                "h32": torch.zeros(mb * W + 4 * mb, dtype=torch.int32).pin_memory(),
-                "hf": torch.zeros(5 * mb, dtype=torch.float32).pin_memory(),
+                "h32": torch.zeros(mb * W + 5 * mb, dtype=torch.int32).pin_memory(),
+                "hf": torch.zeros(6 * mb, dtype=torch.float32).pin_memory(),
                 "tok": torch.zeros(mb, dtype=torch.long).pin_memory(),
                 "lp": torch.zeros(mb, dtype=torch.float32).pin_memory(),
                 "top_ids": torch.zeros(mb, TOP_LOGPROBS, dtype=torch.int32).pin_memory(),
                 "top_lp": torch.zeros(mb, TOP_LOGPROBS, dtype=torch.float32).pin_memory(),
                 "done": None,
+                "bias_set": False, "minp_set": False,   # the set holds non-default bias slots / min_p
             })
+            self._stage[-1]["h32"][mb * W + 4 * mb:].fill_(-1)   # logit_bias slots: none
         self._launches = 0
         # HIPSERVE_STAGE_COPY=blit: per-buffer hipMemcpyAsync instead of the staging kernel
         self._stage_kernel = os.environ.get("HIPSERVE_STAGE_COPY", "kernel") != "blit"
         d64 = torch.zeros(6 * mb, dtype=torch.long, device=dev)
-        d32 = torch.zeros(mb * W + 4 * mb, dtype=torch.int32, device=dev)
-        df = torch.zeros(5 * mb, dtype=torch.float32, device=dev)
+        d32 = torch.zeros(mb * W + 5 * mb, dtype=torch.int32, device=dev)
+        df = torch.zeros(6 * mb, dtype=torch.float32, device=dev)
         st = {
             "d64": d64, "d32": d32, "df": df,
             "ids": d64[0:mb], "pos": d64[mb:2 * mb], "slots": d64[2 * mb:3 * mb],
@@ -736,8 +788,10 @@ class ModelRunner:
             "bt": d32[: mb * W].view(mb, W), "ctx": d32[mb * W: mb * W + mb],
             "topk": d32[mb * W + mb: mb * W + 2 * mb],
             "pslot": d32[mb * W + 2 * mb: mb * W + 3 * mb], "nlp": d32[mb * W + 3 * mb: mb * W + 4 * mb],
+            "bslot": d32[mb * W + 4 * mb: mb * W + 5 * mb],
             "temp": df[0:mb], "topp": df[mb:2 * mb],
             "pres": df[2 * mb:3 * mb], "freq": df[3 * mb:4 * mb], "rep": df[4 * mb:5 * mb],
+            "minp": df[5 * mb:6 * mb],
             "tok": torch.zeros(mb, dtype=torch.long, device=dev),
             "lp": torch.zeros(mb, dtype=torch.float32, device=dev),
             "top_ids": torch.zeros(mb, TOP_LOGPROBS, dtype=torch.int32, device=dev),
@@ -750,6 +804,7 @@ class ModelRunner:
         st["topp"].fill_(1.0)
         st["src"].fill_(-1)
         st["pslot"].fill_(-1)
+        st["bslot"].fill_(-1)
         st["rep"].fill_(1.0)
         t0 = time.time()
         # TP ranks enter the captured collectives together (the tuner and the
@@ -827,11 +882,18 @@ class ModelRunner:
         a32[mb * W: mb * W + n] = inp.ctx_decode
         a32[mb * W + n: mb * W + b] = 1
         a32[mb * W + mb: mb * W + mb + n] = inp.top_k
-        o = mb * W + 2 * mb  # penalty slots, then top-n logprobs counts
+        o = mb * W + 2 * mb  # penalty slots, then top-n logprobs counts, then logit_bias slots
         a32[o:o + n] = inp.pen_slot if inp.pen_slot is not None else -1
         a32[o + n:o + b] = -1
         a32[o + mb:o + mb + n] = inp.nlogprobs if inp.nlogprobs is not None else 0
         a32[o + mb + n:o + mb + b] = 0
+        # logit_bias slots and min_p: a staging set keeps their defaults (-1 / 0) between the
+        # steps that use them, so the common step writes neither region
+        if inp.bias_slot is not None or sg["bias_set"]:
+            a32[o + 2 * mb:o + 3 * mb] = -1
+            sg["bias_set"] = inp.bias_slot is not None
+            if sg["bias_set"]:
+                a32[o + 2 * mb:o + 2 * mb + n] = inp.bias_slot
         af = hf.numpy()
         af[0:n] = inp.temperature
         af[n:b] = 0.0
@@ -844,8 +906,13 @@ class ModelRunner:
             af[2 * mb:2 * mb + n] = 0.0
             af[3 * mb:3 * mb + n] = 0.0
             af[4 * mb:4 * mb + n] = 1.0
+        if inp.min_p is not None or sg["minp_set"]:
+            af[5 * mb:6 * mb] = 0.0
+            sg["minp_set"] = inp.min_p is not None
+            if sg["minp_set"]:
+                af[5 * mb:5 * mb + n] = inp.min_p
         st = self._static
-        full = (inp.pen_slot is not None or inp.nlogprobs is not None
+        full = (inp.pen_slot is not None or inp.nlogprobs is not None or inp.bias_slot is not None
                 or bool(np.any((inp.top_k[:n] > 0) & (inp.top_p[:n] < 1.0))))
         if self._stage_kernel:  # the graph of this parity stages in/out itself
             self.graphs[(b, (self._launches - 1) & 1, full)].replay()

@@ -10,6 +10,7 @@ INT32_MAX = (1 << 31) - 1
 MAX_LOGPROBS = 20   # OpenAI's top_logprobs limit; also the sampler kernel's top-n capacity
 MAX_N = 128
 MAX_STOP = 64
+MAX_LOGIT_BIAS = 300   # OpenAI's logit_bias limit; also the width of a device bias slot
 
 
 def _int(name: str, v, lo: int, hi: int) -> int:
@@ -41,6 +42,30 @@ def _float(name: str, v, lo: float, hi: float) -> float:
     return v
 
 
+def _logit_bias(v) -> list[tuple[int, float]]:
+    """OpenAI ``logit_bias`` ({token id (int or string): bias in [-100, 100]}) as a
+    list of (id, bias) sorted by id; the normalised list itself is accepted again
+    (``SamplingParams(**params.__dict__)``). Ids are checked against the vocabulary
+    where a model is known (``LLMEngine.add_request``, the HTTP handler)."""
+    if v is None:
+        return []
+    if isinstance(v, dict):
+        items = list(v.items())
+    elif isinstance(v, list) and all(isinstance(e, tuple) and len(e) == 2 for e in v):
+        items = v
+    else:
+        raise ValueError("logit_bias must be an object mapping token ids to biases")
+    if len(items) > MAX_LOGIT_BIAS:
+        raise ValueError(f"logit_bias: at most {MAX_LOGIT_BIAS} entries")
+    out = {}
+    for k, b in items:
+        t = _int("logit_bias token id", k, 0, INT32_MAX)
+        if t in out:
+            raise ValueError(f"logit_bias: token id {t} given more than once")
+        out[t] = _float("logit_bias value", b, -100.0, 100.0)
+    return sorted(out.items())
+
+
 @dataclass
 class SamplingParams:
     temperature: float = 1.0
@@ -57,6 +82,8 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     logprobs: int | None = None
     n: int = 1
+    min_p: float = 0.0          # keep tokens with p >= min_p * p_max (after top-k / top-p); 0: off
+    logit_bias: object = None   # {token id: bias}; normalised to a sorted list of (id, bias)
 
     def __post_init__(self):
         """Coerce and range-check every field: a value that reaches the engine
@@ -90,10 +117,18 @@ class SamplingParams:
         if self.logprobs is not None:
             self.logprobs = _int("logprobs", self.logprobs, 0, MAX_LOGPROBS)
         self.n = _int("n", self.n, 1, MAX_N)
+        self.min_p = _float("min_p", self.min_p, 0.0, 1.0)
+        self.logit_bias = _logit_bias(self.logit_bias)
 
     @property
     def greedy(self) -> bool:
         return self.temperature <= 1e-5
+
+    def check_vocab(self, vocab_size: int):
+        """logit_bias ids must name tokens of the model."""
+        for t, _ in self.logit_bias:
+            if t >= vocab_size:
+                raise ValueError(f"logit_bias token id out of range [0, {vocab_size})")
 
     @property
     def has_penalties(self) -> bool:
@@ -127,6 +162,7 @@ class Sequence:
     last_token_time: float | None = None
     seed: int = 0
     pen_slot: int | None = None         # device penalty-state slot (ModelRunner), while it has penalties
+    bias_slot: int | None = None        # device logit_bias slot (ModelRunner), while it has a bias
     mm: object = None                   # multimodal.MMState of a prompt with images
     # detokenizer state
     output_text: str = ""

@@ -99,13 +99,18 @@ class KernelOps:
                                    nq, nkv, scale, window)
         return out
 
-    def sample(self, out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds=True):
+    def sample(self, out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds=True,
+               min_p=None):
         """two_rounds=False: no row combines top-k with top-p (the multi-CU sampler's
-        second fine-histogram round is then a no-op and is not launched)."""
-        self._op.sample(out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds)
+        second fine-histogram round is then a no-op and is not launched).
+        min_p: float [rows] or None; rows with min_p <= 0 sample as without it."""
+        self._op.sample(out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds, min_p)
 
     def penalty_apply(self, logits, slot, pres, freq, rep, counts, seen):
         self._op.penalty_apply(logits, slot, pres, freq, rep, counts, seen)
+
+    def logit_bias_apply(self, logits, slot, ids, vals, n):
+        self._op.logit_bias_apply(logits, slot, ids, vals, n)
 
     def penalty_update(self, tok, slot, counts, seen):
         self._op.penalty_update(tok, slot, counts, seen)
@@ -196,6 +201,9 @@ class ReferenceOps:
     def penalty_apply(self, logits, slot, pres, freq, rep, counts, seen):
         ref.penalty_apply(logits, slot, pres, freq, rep, counts, seen)
 
+    def logit_bias_apply(self, logits, slot, ids, vals, n):
+        ref.logit_bias_apply(logits, slot, ids, vals, n)
+
     def penalty_update(self, tok, slot, counts, seen):
         ref.penalty_update(tok, slot, counts, seen)
 
@@ -224,8 +232,9 @@ class ReferenceOps:
         out.copy_(ref.vision_attention(qkv, cu_seqlens, nh, D, scale))
         return out
 
-    def sample(self, out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds=True):
-        t, lp = ref.sample(logits, temperature, top_k, top_p, seeds, steps, bf16_row=False)
+    def sample(self, out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds=True,
+               min_p=None):
+        t, lp = ref.sample(logits, temperature, top_k, top_p, seeds, steps, bf16_row=False, min_p=min_p)
         n = t.shape[0]
         out_tok[:n].copy_(t)
         if out_lp.numel():

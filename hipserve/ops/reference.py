@@ -247,11 +247,34 @@ def uniform01(seed: int, step: int, n: int) -> np.ndarray:
     return (((h >> np.uint32(8)).astype(np.float64) + 0.5) / 16777216.0).astype(np.float32)
 
 
-def sample(logits: torch.Tensor, temperature, top_k, top_p, seeds, steps, bf16_row: bool = True):
+def sample_keep(x: torch.Tensor, t: float, k: int, p: float, mp: float = 0.0) -> torch.Tensor:
+    """Survivor mask of one fp32 row x at temperature t > 0: top-k, then top-p on the
+    top-k survivors' mass, then min_p (p_i >= mp * p_max, i.e. (x - max) / t >= ln mp;
+    it does not move the two thresholds before it, and the row maximum always survives)."""
+    V = x.shape[0]
+    keep = torch.ones(V, dtype=torch.bool)
+    if 0 < k < V:
+        kth = torch.topk(x, k).values[-1]
+        keep &= x >= kth
+    if p < 1.0:
+        w = torch.exp((x - x.max()) / t) * keep
+        order = torch.argsort(x, descending=True)
+        cum = torch.cumsum(w[order].double(), 0)
+        target = p * float(cum[-1])
+        n = int(torch.searchsorted(cum, torch.tensor([target], dtype=torch.float64))[0])
+        thr = x[order[min(n, V - 1)]]
+        keep &= x >= thr
+    if mp > 0.0:
+        keep &= (x - x.max()) / t >= min(math.log(mp), 0.0)
+    return keep
+
+
+def sample(logits: torch.Tensor, temperature, top_k, top_p, seeds, steps, bf16_row: bool = True, min_p=None):
     """Returns (tokens int64 [B], logprobs f32 [B]) with the kernel's semantics:
-    greedy if T<=1e-5; else top-k then top-p (on the top-k-renormalised mass) then
-    a Gumbel-max draw with u = hash(seed, step, index). ``bf16_row`` mirrors the
-    kernel, which holds an fp32 row as bf16; the CPU engine samples full fp32."""
+    greedy if T<=1e-5; else top-k then top-p (on the top-k-renormalised mass), then
+    min_p (``sample_keep``), then a Gumbel-max draw with u = hash(seed, step, index).
+    ``bf16_row`` mirrors the kernel, which holds an fp32 row as bf16; the CPU engine
+    samples full fp32."""
     B, V = logits.shape
     toks = torch.empty(B, dtype=torch.long)
     lps = torch.empty(B, dtype=torch.float32)
@@ -267,20 +290,7 @@ def sample(logits: torch.Tensor, temperature, top_k, top_p, seeds, steps, bf16_r
             i = int(torch.argmax(x))
             toks[r], lps[r] = i, float(x[i] - lse)
             continue
-        keep = torch.ones(V, dtype=torch.bool)
-        k = int(top_k[r])
-        if 0 < k < V:
-            kth = torch.topk(x, k).values[-1]
-            keep &= x >= kth
-        p = float(top_p[r])
-        if p < 1.0:
-            w = torch.exp((x - x.max()) / t) * keep
-            order = torch.argsort(x, descending=True)
-            cum = torch.cumsum(w[order].double(), 0)
-            target = p * float(cum[-1])
-            n = int(torch.searchsorted(cum, torch.tensor([target], dtype=torch.float64))[0])
-            thr = x[order[min(n, V - 1)]]
-            keep &= x >= thr
+        keep = sample_keep(x, t, int(top_k[r]), float(top_p[r]), float(min_p[r]) if min_p is not None else 0.0)
         u = torch.from_numpy(uniform01(int(seeds[r]), int(steps[r]), V))
         g = (x - x.max()) / t - torch.log(-torch.log(u))
         g = torch.where(keep, g, torch.full_like(g, float("-inf")))
@@ -337,6 +347,24 @@ def penalty_apply(logits, slot, pres, freq, rep, counts, seen):
         c = counts[s].float()
         l = l - f * c - p * (c > 0).float()
         logits[r].copy_(l.to(logits.dtype))
+    return logits
+
+
+def logit_bias_apply(logits, slot, ids, vals, n):
+    """OpenAI logit_bias: row r with slot s >= 0 gets logits[r, ids[s, e]] += vals[s, e]
+    for e < n[s] (fp32 add, stored in the logits' dtype; ids unique within a slot)."""
+    rows, V = logits.shape
+    for r in range(rows):
+        s = int(slot[r])
+        if s < 0:
+            continue
+        c = min(int(n[s]), ids.shape[1])
+        if c <= 0:
+            continue
+        i, v = ids[s, :c].long(), vals[s, :c].float()
+        ok = (i >= 0) & (i < V)
+        i, v = i[ok], v[ok]
+        logits[r, i] = (logits[r, i].float() + v).to(logits.dtype)
     return logits
 
 

@@ -133,14 +133,25 @@ class OpenAIServer:
             v = body.get(key)
             return default if v is None else v
 
+        bias = body.get("logit_bias")
+        if bias is not None and not isinstance(bias, dict):
+            raise ValueError("logit_bias must be an object mapping token ids to biases")
         # SamplingParams coerces and range-checks every field (ValueError -> 400)
-        return SamplingParams(
+        params = SamplingParams(
             temperature=opt("temperature", 1.0), top_p=opt("top_p", 1.0), top_k=opt("top_k", 0),
             max_tokens=mt, min_tokens=opt("min_tokens", 0), stop=opt("stop", []),
             stop_token_ids=stop_ids, ignore_eos=bool(body.get("ignore_eos", False)),
             seed=body.get("seed"), presence_penalty=opt("presence_penalty", 0.0),
             frequency_penalty=opt("frequency_penalty", 0.0),
-            repetition_penalty=opt("repetition_penalty", 1.0), logprobs=lp, n=opt("n", 1))
+            repetition_penalty=opt("repetition_penalty", 1.0), logprobs=lp, n=opt("n", 1),
+            min_p=opt("min_p", 0.0), logit_bias=bias)
+        self._check_bias(params)
+        return params
+
+    def _check_bias(self, params: SamplingParams):
+        """logit_bias ids outside the vocabulary: a 400 before any SSE header goes out,
+        as for prompt ids."""
+        params.check_vocab(self.engine.model_cfg.vocab_size)
 
     def _check_prompt(self, ids):
         """The engine's add_request checks, run in the handler so that a bad prompt

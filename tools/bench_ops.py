@@ -82,6 +82,22 @@ def bench_sample(ops):
             steps = torch.zeros(B, dtype=torch.long, device=DEV)
             us = timer(lambda: ops.sample(tok, lp, logits, temp, tk, tp, seeds, steps))
             emit(op="sample", mode=name, V=V, B=B, us=round(us, 1), graph=timer is graph_time)
+        # temperature sampling with a min_p cut on every row
+        temp = torch.full((B,), 0.8, device=DEV)
+        tk = torch.zeros(B, dtype=torch.int32, device=DEV)
+        tp = torch.ones(B, device=DEV)
+        mp = torch.full((B,), 0.05, device=DEV)
+        us = timer(lambda: ops.sample(tok, lp, logits, temp, tk, tp, seeds, steps, min_p=mp))
+        emit(op="sample", mode="min_p", V=V, B=B, us=round(us, 1), graph=timer is graph_time)
+    # logit_bias_apply: 64 rows, every row with a full 300-entry slot
+    V, B, E = 128256, 64, 300
+    logits = (torch.randn(B, V, device=DEV) * 3).to(torch.bfloat16)
+    ids = torch.stack([torch.randperm(V, device=DEV)[:E] for _ in range(B)]).int()
+    vals = torch.rand(B, E, device=DEV) * 2 - 1
+    n = torch.full((B,), E, dtype=torch.int32, device=DEV)
+    slot = torch.arange(B, dtype=torch.int32, device=DEV)
+    us = timer(lambda: ops.logit_bias_apply(logits, slot, ids, vals, n))
+    emit(op="logit_bias_apply", V=V, B=B, entries=E, us=round(us, 1), graph=timer is graph_time)
 
 
 def bench_decode(ops):
