@@ -165,26 +165,6 @@ HS_DEVICE typename KvVec<KV>::T kv_load8_nt(const KV* p) {
   return __builtin_nontemporal_load(reinterpret_cast<const typename KvVec<KV>::T*>(p));
 }
 
-template <int VPT, int NT>
-HS_DEVICE void row_e4m3(const u16x8 (&ov)[VPT], int nvec, int row, int N, unsigned char* __restrict__ out8,
-                        float* __restrict__ xs8, float* scratch) {
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPT; ++i)
-    if (threadIdx.x + i * NT < nvec)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(bf16_to_f32(ov[i][j])));
-  __syncthreads();  // scratch was the norm's reduction buffer
-  amax = block_max(amax, scratch);
-  const float inv = amax > 0.f ? 448.f / amax : 1.f;
-  if (threadIdx.x == 0) xs8[row] = amax > 0.f ? amax / 448.f : 1.f;
-#pragma unroll
-  for (int i = 0; i < VPT; ++i) {
-    const int idx = threadIdx.x + i * NT;
-    if (idx < nvec) *reinterpret_cast<uint2*>(out8 + (long)row * N + idx * 8) = e4m3_8(ov[i], inv);
-  }
-}
-
 HS_HOST_DEVICE int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // SiLU(gate) * up on 8 bf16 lanes, fp32 math, one bf16 rounding (shared by the
@@ -215,12 +195,6 @@ HS_DEVICE u16x8 gelu_mul8(const u16x8 g, const u16x8 u) {
   for (int j = 0; j < 8; ++j) o[j] = gelu_mul1(g[j], u[j]);
   return o;
 }
-
-// Row-norm launch policy shared by every RMSNorm-family kernel (norm.hip,
-// decode_fused.hip) so they reduce in the same order and stay bit-identical:
-// 512 threads from 4096 columns up (more loads in flight on the 1-row-per-CU
-// decode shapes), 256 below.
-HS_HOST_DEVICE int norm_threads(int hidden) { return hidden >= 4096 ? 512 : 256; }
 
 // Bijective XCD-aware block remap (MI355X: 8 XCDs, blocks dealt round-robin).
 // Blocks that share operand panels end up on the same XCD's L2.

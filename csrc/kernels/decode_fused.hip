@@ -12,13 +12,11 @@
 //     k / v into the paged cache.
 // Both round exactly where the unfused chain rounds (bf16 after the sum, bf16
 // residual), so the fused and unfused decode paths are bit-identical.
-#include "hipserve/common.h"
 #include "hipserve/kernels.h"
+#include "hipserve/row_norm.h"
 
 namespace hipserve {
 
-// sum over S slices of 8 consecutive fp32 partials (batched loads, common.h),
-// rounded to bf16 like the unfused reduce output, returned as fp32
 // x = bf16(x + b) for 8 bf16 bias values (torch's bf16 add of the bias vector)
 HS_DEVICE void add_bias8(float (&x)[8], const unsigned short* __restrict__ b) {
   const u16x8 v = *reinterpret_cast<const u16x8*>(b);
@@ -26,17 +24,8 @@ HS_DEVICE void add_bias8(float (&x)[8], const unsigned short* __restrict__ b) {
   for (int j = 0; j < 8; ++j) x[j] = bf16_to_f32(f32_to_bf16(x[j] + bf16_to_f32(v[j])));
 }
 
-// 8 bf16 values -> f16 in the quantised decode GEMM's staging pair order
-// {0, 2, 1, 3, 4, 6, 5, 7} (gguf_mfma.hip kX16): bf16 -> fp32 exact, -> f16 round to
-// nearest — the conversion the GEMM would otherwise run in every workgroup
-HS_DEVICE u16x8 f16_pairs8(const u16x8 v) {
-  constexpr int ord[8] = {0, 2, 1, 3, 4, 6, 5, 7};
-  u16x8 h;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) h[j] = __builtin_bit_cast(unsigned short, static_cast<_Float16>(bf16_to_f32(v[ord[j]])));
-  return h;
-}
-
+// sum over S slices of 8 consecutive fp32 partials (batched loads, common.h),
+// rounded to bf16 like the unfused reduce output, returned as fp32
 HS_DEVICE void sum8_bf16(float (&o)[8], const float* __restrict__ p, long slice, int S) {
   f32x4 lo, hi;
   sum_slices8(lo, hi, p, slice, S);
@@ -61,20 +50,14 @@ __global__ __launch_bounds__(NT) void splitk_add_rmsnorm_kernel(unsigned short* 
   const long slice = (long)M * N;
   // the norm weight and the residual do not depend on the reduction: issue their
   // loads first and keep them raw, so no s_waitcnt sits in front of the partials
-  f32x4 wf[VPT][2];
-  u16x8 wb[VPT], res[VPT];
+  NormW8Raw<kWF32> wraw[VPT];
+  u16x8 res[VPT];
   u16x8* rr = reinterpret_cast<u16x8*>(residual + (long)row * N);
 #pragma unroll
   for (int i = 0; i < VPT; ++i) {
     const int idx = threadIdx.x + i * NT;
     if (idx < nvec) {
-      if constexpr (kWF32) {
-        const f32x4* wp = reinterpret_cast<const f32x4*>(weight) + idx * 2;
-        wf[i][0] = wp[0];
-        wf[i][1] = wp[1];
-      } else {
-        wb[i] = reinterpret_cast<const u16x8*>(weight)[idx];
-      }
+      wraw[i] = norm_w8_load<kWF32>(weight, idx);
       res[i] = rr[idx];
     }
   }
@@ -96,44 +79,9 @@ __global__ __launch_bounds__(NT) void splitk_add_rmsnorm_kernel(unsigned short* 
       rr[idx] = r;
     }
   }
-  ss = block_sum(ss, scratch);
-  const float inv = rsqrtf(ss / N + eps);
-  u16x8* orow = reinterpret_cast<u16x8*>(out + (long)row * N);
-  u16x8 ov[VPT];
-#pragma unroll
-  for (int i = 0; i < VPT; ++i) {
-    const int idx = threadIdx.x + i * NT;
-    if (idx < nvec) {
-      u16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float wj;
-        if constexpr (kWF32) wj = wf[i][j >> 2][j & 3];
-        else wj = bf16_to_f32(wb[i][j]);
-        o[j] = f32_to_bf16(v[i][j] * inv * wj);
-      }
-      orow[idx] = o;
-      ov[i] = o;
-      if (out16 != nullptr) reinterpret_cast<u16x8*>(out16 + (long)row * N)[idx] = f16_pairs8(o);
-    }
-  }
-  if (out8 != nullptr) row_e4m3<VPT, NT>(ov, nvec, row, N, out8, xs8, scratch);
-}
-
-template <bool kWF32>
-static void add_rmsnorm_t(void* out, void* residual, const float* ws, int S, const void* w, int M, int N, float eps,
-                          hipStream_t s, unsigned short* o16, unsigned char* o8, float* x8) {
-  auto* o = static_cast<unsigned short*>(out);
-  auto* r = static_cast<unsigned short*>(residual);
-  const int nvec = N / 8;
-  if (norm_threads(N) == 256) {
-    if (nvec <= 256) splitk_add_rmsnorm_kernel<256, 1, kWF32><<<M, 256, 0, s>>>(o, r, ws, S, w, M, N, eps, o16, o8, x8);
-    else splitk_add_rmsnorm_kernel<256, 2, kWF32><<<M, 256, 0, s>>>(o, r, ws, S, w, M, N, eps, o16, o8, x8);
-  } else {
-    if (nvec <= 512) splitk_add_rmsnorm_kernel<512, 1, kWF32><<<M, 512, 0, s>>>(o, r, ws, S, w, M, N, eps, o16, o8, x8);
-    else if (nvec <= 1024) splitk_add_rmsnorm_kernel<512, 2, kWF32><<<M, 512, 0, s>>>(o, r, ws, S, w, M, N, eps, o16, o8, x8);
-    else splitk_add_rmsnorm_kernel<512, 4, kWF32><<<M, 512, 0, s>>>(o, r, ws, S, w, M, N, eps, o16, o8, x8);
-  }
+  row_norm_finish<NT, VPT>(
+      v, ss, [&](float (&w)[8], int i, int) { norm_w8<kWF32>(w, wraw[i]); }, out, N, row, N, eps, out16, out8, xs8,
+      scratch);
 }
 
 void launch_splitk_add_rmsnorm(void* out, void* residual, const float* ws, int S, const void* w, bool weight_f32,
@@ -141,8 +89,10 @@ void launch_splitk_add_rmsnorm(void* out, void* residual, const float* ws, int S
   if (M <= 0) return;
   auto* o16 = static_cast<unsigned short*>(out16);
   auto* o8 = static_cast<unsigned char*>(out8);
-  if (weight_f32) add_rmsnorm_t<true>(out, residual, ws, S, w, M, N, eps, s, o16, o8, xs8);
-  else add_rmsnorm_t<false>(out, residual, ws, S, w, M, N, eps, s, o16, o8, xs8);
+  row_norm_dispatch(N, weight_f32, [&](auto nt, auto vpt, auto wf) {
+    splitk_add_rmsnorm_kernel<nt(), vpt(), wf()><<<M, nt(), 0, s>>>(
+        static_cast<unsigned short*>(out), static_cast<unsigned short*>(residual), ws, S, w, M, N, eps, o16, o8, xs8);
+  });
 }
 
 // Sandwich-norm epilogue (Gemma-3: post-attention / post-feedforward RMSNorm on the
@@ -151,23 +101,6 @@ void launch_splitk_add_rmsnorm(void* out, void* residual, const float* ws, int S
 // unfused chain splitk_reduce -> rmsnorm -> fused_add_rmsnorm in one kernel, with each
 // norm reduced in the row-norm kernels' order (same thread -> element map), so the
 // result is bit-identical.
-template <bool kWF32>
-HS_DEVICE void norm_w8(float (&w)[8], const void* __restrict__ weight, int idx) {
-  if constexpr (kWF32) {
-    const f32x4* wp = reinterpret_cast<const f32x4*>(weight) + idx * 2;
-    const f32x4 w0 = wp[0], w1 = wp[1];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      w[j] = w0[j];
-      w[j + 4] = w1[j];
-    }
-  } else {
-    const u16x8 wv = reinterpret_cast<const u16x8*>(weight)[idx];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) w[j] = bf16_to_f32(wv[j]);
-  }
-}
-
 template <int NT, int VPT, bool kWF32>
 __global__ __launch_bounds__(NT) void splitk_post_add_rmsnorm_kernel(unsigned short* __restrict__ out,
                                                                       unsigned short* __restrict__ residual,
@@ -219,42 +152,9 @@ __global__ __launch_bounds__(NT) void splitk_post_add_rmsnorm_kernel(unsigned sh
       rr[idx] = r;
     }
   }
-  ss2 = block_sum(ss2, scratch);
-  const float inv2 = rsqrtf(ss2 / N + eps);
-  u16x8* orow = reinterpret_cast<u16x8*>(out + (long)row * N);
-  u16x8 ov[VPT];
-#pragma unroll
-  for (int i = 0; i < VPT; ++i) {
-    const int idx = threadIdx.x + i * NT;
-    if (idx < nvec) {
-      float w[8];
-      norm_w8<kWF32>(w, w_next, idx);
-      u16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = f32_to_bf16(v[i][j] * inv2 * w[j]);
-      orow[idx] = o;
-      ov[i] = o;
-      if (out16 != nullptr) reinterpret_cast<u16x8*>(out16 + (long)row * N)[idx] = f16_pairs8(o);
-    }
-  }
-  if (out8 != nullptr) row_e4m3<VPT, NT>(ov, nvec, row, N, out8, xs8, scratch);
-}
-
-template <bool kWF32>
-static void post_add_rmsnorm_t(void* out, void* residual, const float* ws, int S, const void* wp, const void* wn,
-                               int M, int N, float eps, hipStream_t s, unsigned short* o16, unsigned char* o8,
-                               float* x8) {
-  auto* o = static_cast<unsigned short*>(out);
-  auto* r = static_cast<unsigned short*>(residual);
-  const int nvec = N / 8;
-  if (norm_threads(N) == 256) {
-    if (nvec <= 256) splitk_post_add_rmsnorm_kernel<256, 1, kWF32><<<M, 256, 0, s>>>(o, r, ws, S, wp, wn, M, N, eps, o16, o8, x8);
-    else splitk_post_add_rmsnorm_kernel<256, 2, kWF32><<<M, 256, 0, s>>>(o, r, ws, S, wp, wn, M, N, eps, o16, o8, x8);
-  } else {
-    if (nvec <= 512) splitk_post_add_rmsnorm_kernel<512, 1, kWF32><<<M, 512, 0, s>>>(o, r, ws, S, wp, wn, M, N, eps, o16, o8, x8);
-    else if (nvec <= 1024) splitk_post_add_rmsnorm_kernel<512, 2, kWF32><<<M, 512, 0, s>>>(o, r, ws, S, wp, wn, M, N, eps, o16, o8, x8);
-    else splitk_post_add_rmsnorm_kernel<512, 4, kWF32><<<M, 512, 0, s>>>(o, r, ws, S, wp, wn, M, N, eps, o16, o8, x8);
-  }
+  row_norm_finish<NT, VPT>(
+      v, ss2, [&](float (&w)[8], int, int idx) { norm_w8<kWF32>(w, w_next, idx); }, out, N, row, N, eps, out16, out8,
+      xs8, scratch);
 }
 
 void launch_splitk_post_add_rmsnorm(void* out, void* residual, const float* ws, int S, const void* w_post,
@@ -263,8 +163,11 @@ void launch_splitk_post_add_rmsnorm(void* out, void* residual, const float* ws, 
   if (M <= 0) return;
   auto* o16 = static_cast<unsigned short*>(out16);
   auto* o8 = static_cast<unsigned char*>(out8);
-  if (weight_f32) post_add_rmsnorm_t<true>(out, residual, ws, S, w_post, w_next, M, N, eps, s, o16, o8, xs8);
-  else post_add_rmsnorm_t<false>(out, residual, ws, S, w_post, w_next, M, N, eps, s, o16, o8, xs8);
+  row_norm_dispatch(N, weight_f32, [&](auto nt, auto vpt, auto wf) {
+    splitk_post_add_rmsnorm_kernel<nt(), vpt(), wf()>
+        <<<M, nt(), 0, s>>>(static_cast<unsigned short*>(out), static_cast<unsigned short*>(residual), ws, S, w_post,
+                            w_next, M, N, eps, o16, o8, xs8);
+  });
 }
 
 // The rope_cache kernel (rope_cache.hip) reading its input from the split-K

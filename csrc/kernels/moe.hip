@@ -15,6 +15,7 @@
 //   moe_combine       y rows of a token's k pairs, weighted sum -> hidden state
 #include "hipserve/common.h"
 #include "hipserve/kernels.h"
+#include "hipserve/row_norm.h"
 
 namespace hipserve {
 
@@ -403,59 +404,22 @@ __global__ __launch_bounds__(NT) void moe_combine_add_rmsnorm_kernel(
       for (int e = 0; e < 8; ++e) ss += v[i][e] * v[i][e];
     }
   }
-  ss = block_sum(ss, scratch);
-  const float inv = rsqrtf(ss / H + eps);
-  u16x8* orow = reinterpret_cast<u16x8*>(out + (long)t * H);
-#pragma unroll
-  for (int i = 0; i < VPT; ++i) {
-    const int idx = threadIdx.x + i * NT;
-    if (idx < nvec) {
-      float wv[8];
-      if constexpr (kWF32) {
-        const f32x4* wp = reinterpret_cast<const f32x4*>(weight) + idx * 2;
-        const f32x4 w0 = wp[0], w1 = wp[1];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { wv[e] = w0[e]; wv[e + 4] = w1[e]; }
-      } else {
-        const u16x8 wb = reinterpret_cast<const u16x8*>(weight)[idx];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) wv[e] = bf16_to_f32(wb[e]);
-      }
-      u16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = f32_to_bf16(v[i][e] * inv * wv[e]);
-      orow[idx] = o;
-    }
-  }
-}
-
-template <bool kWF32, bool kPartial>
-static void mcn_launch(void* out, void* residual, const void* y, long slab, int S, const float* w, const int* ps,
-                       int T, int k, int H, const void* nw, float eps, hipStream_t s) {
-  auto* o = static_cast<unsigned short*>(out);
-  auto* r = static_cast<unsigned short*>(residual);
-  const int nvec = H / 8;
-  if (norm_threads(H) == 256) {
-    if (nvec <= 256) moe_combine_add_rmsnorm_kernel<256, 1, kWF32, kPartial><<<T, 256, 0, s>>>(o, r, y, slab, S, w, ps, k, H, nw, eps);
-    else moe_combine_add_rmsnorm_kernel<256, 2, kWF32, kPartial><<<T, 256, 0, s>>>(o, r, y, slab, S, w, ps, k, H, nw, eps);
-  } else {
-    if (nvec <= 512) moe_combine_add_rmsnorm_kernel<512, 1, kWF32, kPartial><<<T, 512, 0, s>>>(o, r, y, slab, S, w, ps, k, H, nw, eps);
-    else if (nvec <= 1024) moe_combine_add_rmsnorm_kernel<512, 2, kWF32, kPartial><<<T, 512, 0, s>>>(o, r, y, slab, S, w, ps, k, H, nw, eps);
-    else moe_combine_add_rmsnorm_kernel<512, 4, kWF32, kPartial><<<T, 512, 0, s>>>(o, r, y, slab, S, w, ps, k, H, nw, eps);
-  }
+  row_norm_finish<NT, VPT>(
+      v, ss, [&](float (&nw)[8], int, int idx) { norm_w8<kWF32>(nw, weight, idx); }, out, H, t, H, eps, nullptr,
+      nullptr, nullptr, scratch);
 }
 
 void launch_moe_combine_add_rmsnorm(void* out, void* residual, const void* y, long slab, int S, const float* w,
                                     const int* pair_slot, int T, int k, int H, const void* norm_w, bool norm_f32,
                                     float eps, hipStream_t s) {
   if (T <= 0) return;
-  if (S > 0) {
-    if (norm_f32) mcn_launch<true, true>(out, residual, y, slab, S, w, pair_slot, T, k, H, norm_w, eps, s);
-    else mcn_launch<false, true>(out, residual, y, slab, S, w, pair_slot, T, k, H, norm_w, eps, s);
-  } else {
-    if (norm_f32) mcn_launch<true, false>(out, residual, y, slab, 0, w, pair_slot, T, k, H, norm_w, eps, s);
-    else mcn_launch<false, false>(out, residual, y, slab, 0, w, pair_slot, T, k, H, norm_w, eps, s);
-  }
+  bool_dispatch(S > 0, [&](auto partial) {
+    row_norm_dispatch(H, norm_f32, [&](auto nt, auto vpt, auto wf) {
+      moe_combine_add_rmsnorm_kernel<nt(), vpt(), wf(), partial()>
+          <<<T, nt(), 0, s>>>(static_cast<unsigned short*>(out), static_cast<unsigned short*>(residual), y, slab,
+                              S > 0 ? S : 0, w, pair_slot, k, H, norm_w, eps);
+    });
+  });
 }
 
 void launch_moe_topk_softmax(const void* logits, bool logits_f32, float* w, int* ids, int T, int E, int k,

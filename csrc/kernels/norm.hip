@@ -1,12 +1,12 @@
 // RMSNorm and fused residual-add + RMSNorm.
 //
-// One 256/512-thread workgroup per token row (norm_threads, common.h); each lane owns VPT 16-byte vectors of
-// the row, held in registers between the sum-of-squares pass and the scale
+// One 256/512-thread workgroup per token row (row_norm.h); each lane owns VPT 16-byte
+// vectors of the row, held in registers between the sum-of-squares pass and the scale
 // pass, so the row is read from HBM exactly once and written once.
 // fp32 accumulation, bf16 I/O. Weight may be bf16 (HF checkpoints) or fp32
 // (GGUF stores norm weights as F32).
-#include "hipserve/common.h"
 #include "hipserve/kernels.h"
+#include "hipserve/row_norm.h"
 
 namespace hipserve {
 
@@ -75,56 +75,10 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(
       for (int j = 0; j < 8; ++j) ss += v[i][j] * v[i][j];
     }
   }
-  ss = block_sum(ss, scratch);
-  const float inv = rsqrtf(ss / hidden + eps);
-  u16x8* orow = reinterpret_cast<u16x8*>(out + row * out_stride);
-  u16x8 ov[VPT];
-#pragma unroll
-  for (int i = 0; i < VPT; ++i) {
-    const int idx = threadIdx.x + i * NT;
-    if (idx < nvec) {
-      float w[8];
-      if constexpr (kWF32) {
-        const f32x4* wp = reinterpret_cast<const f32x4*>(weight) + idx * 2;
-        f32x4 w0 = wp[0], w1 = wp[1];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { w[j] = w0[j]; w[j + 4] = w1[j]; }
-      } else {
-        u16x8 wv = reinterpret_cast<const u16x8*>(weight)[idx];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) w[j] = bf16_to_f32(wv[j]);
-      }
-      u16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = f32_to_bf16(v[i][j] * inv * w[j]);
-      orow[idx] = o;
-      ov[i] = o;
-    }
-  }
-  // optional per-token e4m3 copy (the FP8 W8A8 GEMM's input, = act_quant_fp8 of out)
-  if (out8 != nullptr) row_e4m3<VPT, NT>(ov, nvec, row, hidden, out8, xs8, scratch);
-}
-
-template <bool kAdd, bool kWF32>
-static void launch_rmsnorm_t(unsigned short* out, unsigned short* residual,
-                             const unsigned short* x, const void* w, int rows,
-                             int hidden, long x_stride, long out_stride, float eps,
-                             hipStream_t s, unsigned char* o8, float* x8) {
-  const int nvec = hidden / 8;
-  dim3 grid(rows);
-  if (norm_threads(hidden) == 256) {  // hidden < 4096: nvec < 512
-    if (nvec <= 256)
-      rmsnorm_kernel<256, 1, kAdd, kWF32><<<grid, 256, 0, s>>>(out, residual, x, w, hidden, x_stride, out_stride, eps, GatherIds{}, o8, x8);
-    else
-      rmsnorm_kernel<256, 2, kAdd, kWF32><<<grid, 256, 0, s>>>(out, residual, x, w, hidden, x_stride, out_stride, eps, GatherIds{}, o8, x8);
-  } else {
-    if (nvec <= 512)
-      rmsnorm_kernel<512, 1, kAdd, kWF32><<<grid, 512, 0, s>>>(out, residual, x, w, hidden, x_stride, out_stride, eps, GatherIds{}, o8, x8);
-    else if (nvec <= 1024)
-      rmsnorm_kernel<512, 2, kAdd, kWF32><<<grid, 512, 0, s>>>(out, residual, x, w, hidden, x_stride, out_stride, eps, GatherIds{}, o8, x8);
-    else
-      rmsnorm_kernel<512, 4, kAdd, kWF32><<<grid, 512, 0, s>>>(out, residual, x, w, hidden, x_stride, out_stride, eps, GatherIds{}, o8, x8);
-  }
+  // out8: optional per-token e4m3 copy (the FP8 W8A8 GEMM's input, = act_quant_fp8 of out)
+  row_norm_finish<NT, VPT>(
+      v, ss, [&](float (&w)[8], int, int idx) { norm_w8<kWF32>(w, weight, idx); }, out, out_stride, row, hidden,
+      eps, nullptr, out8, xs8, scratch);
 }
 
 // Per-head RMSNorm of the q and k heads inside the merged qkv rows, in place
@@ -215,28 +169,6 @@ void launch_qk_rmsnorm(void* qkv, long stride, const float* qw, const float* kw,
   qk_rmsnorm_kernel<<<dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s>>>(q, stride, qw, kw, T, nq, nkv, D, eps);
 }
 
-template <bool kWF32>
-static void launch_embed_rmsnorm_t(unsigned short* out, unsigned short* residual, const unsigned short* table,
-                                   const void* w, int rows, int hidden, float eps, GatherIds gi, hipStream_t s,
-                                   unsigned char* o8, float* x8) {
-  const int nvec = hidden / 8;
-  dim3 grid(rows);
-  const long xs = hidden;
-  if (norm_threads(hidden) == 256) {
-    if (nvec <= 256)
-      rmsnorm_kernel<256, 1, false, kWF32, true><<<grid, 256, 0, s>>>(out, residual, table, w, hidden, xs, hidden, eps, gi, o8, x8);
-    else
-      rmsnorm_kernel<256, 2, false, kWF32, true><<<grid, 256, 0, s>>>(out, residual, table, w, hidden, xs, hidden, eps, gi, o8, x8);
-  } else {
-    if (nvec <= 512)
-      rmsnorm_kernel<512, 1, false, kWF32, true><<<grid, 512, 0, s>>>(out, residual, table, w, hidden, xs, hidden, eps, gi, o8, x8);
-    else if (nvec <= 1024)
-      rmsnorm_kernel<512, 2, false, kWF32, true><<<grid, 512, 0, s>>>(out, residual, table, w, hidden, xs, hidden, eps, gi, o8, x8);
-    else
-      rmsnorm_kernel<512, 4, false, kWF32, true><<<grid, 512, 0, s>>>(out, residual, table, w, hidden, xs, hidden, eps, gi, o8, x8);
-  }
-}
-
 void launch_embed_rmsnorm(void* out, void* residual, const void* table, const long* ids, const long* src,
                           const long* tok, const void* w, bool weight_f32, int rows, int hidden, float eps,
                           hipStream_t s, float scale, void* out8, float* xs8) {
@@ -246,8 +178,10 @@ void launch_embed_rmsnorm(void* out, void* residual, const void* table, const lo
   auto* t = static_cast<const unsigned short*>(table);
   auto* o8 = static_cast<unsigned char*>(out8);
   const GatherIds gi{ids, src, tok, scale};
-  if (weight_f32) launch_embed_rmsnorm_t<true>(o, r, t, w, rows, hidden, eps, gi, s, o8, xs8);
-  else launch_embed_rmsnorm_t<false>(o, r, t, w, rows, hidden, eps, gi, s, o8, xs8);
+  row_norm_dispatch(hidden, weight_f32, [&](auto nt, auto vpt, auto wf) {
+    rmsnorm_kernel<nt(), vpt(), false, wf(), true>
+        <<<rows, nt(), 0, s>>>(o, r, t, w, hidden, hidden, hidden, eps, gi, o8, xs8);
+  });
 }
 
 void launch_rmsnorm(void* out, void* residual, const void* x, const void* w,
@@ -257,13 +191,12 @@ void launch_rmsnorm(void* out, void* residual, const void* x, const void* w,
   auto* o = static_cast<unsigned short*>(out);
   auto* r = static_cast<unsigned short*>(residual);
   auto* xi = static_cast<const unsigned short*>(x);
-  if (residual) {
-    if (weight_f32) launch_rmsnorm_t<true, true>(o, r, xi, w, rows, hidden, x_stride, out_stride, eps, s, o8, xs8);
-    else launch_rmsnorm_t<true, false>(o, r, xi, w, rows, hidden, x_stride, out_stride, eps, s, o8, xs8);
-  } else {
-    if (weight_f32) launch_rmsnorm_t<false, true>(o, r, xi, w, rows, hidden, x_stride, out_stride, eps, s, o8, xs8);
-    else launch_rmsnorm_t<false, false>(o, r, xi, w, rows, hidden, x_stride, out_stride, eps, s, o8, xs8);
-  }
+  bool_dispatch(residual != nullptr, [&](auto add) {
+    row_norm_dispatch(hidden, weight_f32, [&](auto nt, auto vpt, auto wf) {
+      rmsnorm_kernel<nt(), vpt(), add(), wf()>
+          <<<rows, nt(), 0, s>>>(o, r, xi, w, hidden, x_stride, out_stride, eps, GatherIds{}, o8, xs8);
+    });
+  });
 }
 
 }  // namespace hipserve

@@ -23,7 +23,8 @@ def _partials(S, M, N, seed):
     return torch.randn(S, M, N, device=DEV, generator=g) * 0.5
 
 
-@pytest.mark.parametrize("M,H", [(1, 4096), (64, 4096), (37, 2048), (8, 8192), (3, 1024), (64, 5376)])
+@pytest.mark.parametrize("M,H", [(1, 4096), (64, 4096), (37, 2048), (8, 8192), (3, 1024), (64, 5376), (2, 2560),
+                                 (2, 8200)])
 @pytest.mark.parametrize("wf32", [False, True])
 @pytest.mark.parametrize("lookahead", [False, True])
 @pytest.mark.parametrize("scale", [1.0, 5376 ** 0.5])
@@ -62,7 +63,8 @@ def test_embed_rmsnorm_bit_exact(ops, M, H, wf32, lookahead, scale):
     assert torch.equal(q8, xq) and torch.equal(s8, xs)
 
 
-@pytest.mark.parametrize("S,M,N", [(1, 5, 4096), (4, 64, 4096), (8, 17, 2048), (3, 1, 8192)])
+@pytest.mark.parametrize("S,M,N", [(1, 5, 4096), (4, 64, 4096), (8, 17, 2048), (3, 1, 8192), (2, 3, 2560),
+                                   (3, 2, 8200)])
 @pytest.mark.parametrize("wf32", [False, True])
 def test_splitk_add_rmsnorm_bit_exact(ops, S, M, N, wf32):
     ws = _partials(S, M, N, S * 100 + M)
@@ -78,6 +80,39 @@ def test_splitk_add_rmsnorm_bit_exact(ops, S, M, N, wf32):
     r2, o2 = res0.clone(), torch.empty_like(res0)
     torch.ops.hipserve.splitk_add_rmsnorm(o2, r2, ws.contiguous(), S, w, 1e-5)
     assert torch.equal(r1, r2) and torch.equal(o1, o2)
+
+
+@pytest.mark.parametrize("N", [1024, 2560, 4096, 5376, 8200])  # one per rung of the row-norm launch ladder
+@pytest.mark.parametrize("M", [1, 5])
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("wf32", [False, True])
+def test_splitk_post_add_rmsnorm_bit_exact(ops, N, M, S, wf32):
+    """The sandwich-norm epilogue == splitk_reduce -> rmsnorm (w_post, in place) ->
+    fused_add_rmsnorm (w_next), bit for bit in the norm output and the updated residual;
+    its out16 is the f16 pair-order copy of that output, its out8 / xs8 act_quant_fp8 of it."""
+    from hipserve.ops import pgemm
+
+    ws = _partials(S, M, N, S * 100 + M + N).contiguous()
+    g = torch.Generator(device=DEV).manual_seed(N + M)
+    res0 = torch.randn(M, N, device=DEV, generator=g).to(torch.bfloat16)
+    wdt = torch.float32 if wf32 else torch.bfloat16
+    w_post = (torch.rand(N, device=DEV, generator=g) + 0.5).to(wdt)
+    w_next = (torch.rand(N, device=DEV, generator=g) + 0.5).to(wdt)
+    h = torch.empty_like(res0)
+    torch.ops.hipserve.splitk_reduce(h, ws, S)
+    ops.rmsnorm(h, h, w_post, 1e-6)
+    r1, o1 = res0.clone(), torch.empty_like(res0)
+    ops.fused_add_rmsnorm(o1, h, r1, w_next, 1e-6)
+    r2, o2 = res0.clone(), torch.full_like(res0, float("nan"))
+    o16 = torch.empty(M, N, device=DEV, dtype=torch.float16)
+    q8 = torch.empty(M, N, device=DEV, dtype=torch.uint8)
+    s8 = torch.empty(M, device=DEV, dtype=torch.float32)
+    torch.ops.hipserve.splitk_post_add_rmsnorm(o2, r2, ws, S, w_post, w_next, 1e-6, o16, q8, s8)
+    assert torch.equal(r1, r2) and torch.equal(o1, o2)
+    pairs = o2.float().to(torch.float16).reshape(M, -1, 8)[:, :, [0, 2, 1, 3, 4, 6, 5, 7]].reshape(M, N)
+    assert torch.equal(o16, pairs)
+    xq, xs = pgemm.act_quant(o2)
+    assert torch.equal(q8, xq) and torch.equal(s8, xs)
 
 
 @pytest.mark.parametrize("mode", [0, 1])

@@ -22,9 +22,12 @@ def _close(a, b, atol, rtol=0.0, frac=1.0):
     assert bad.float().mean().item() <= 1.0 - frac, f"max err {(a - b).abs().max().item()}"
 
 
-@pytest.mark.parametrize("rows,hidden", [(7, 4096), (33, 8192), (3, 2048), (1, 64)])
+@pytest.mark.parametrize("rows,hidden", [(7, 4096), (33, 8192), (3, 2048), (1, 64), (3, 2560), (2, 8200)])
 @pytest.mark.parametrize("wf32", [False, True])
 def test_rmsnorm(ops, rows, hidden, wf32):
+    """The row-norm family's one test against the CPU reference: the other three kernels
+    are compared bit for bit to these two ops. 2560 and 8200 run the (256, 2) and
+    (512, 4) rungs of the launch ladder with a partly filled last vector slot."""
     torch.manual_seed(0)
     x = torch.randn(rows, hidden, device=DEV, dtype=torch.bfloat16)
     w = torch.randn(hidden, device=DEV, dtype=torch.float32 if wf32 else torch.bfloat16)
@@ -375,7 +378,8 @@ def test_moe_topk_softmax_from_partials(ops, T, E, k, S):
     assert torch.equal(i0, i1) and torch.equal(w0, w1)
 
 
-@pytest.mark.parametrize("T,k,H", [(1, 8, 2048), (37, 8, 2048), (256, 2, 4096), (5, 4, 7168), (9, 2, 1024)])
+@pytest.mark.parametrize("T,k,H", [(1, 8, 2048), (37, 8, 2048), (256, 2, 4096), (5, 4, 7168), (9, 2, 1024),
+                                   (3, 2, 2560), (2, 2, 8200)])
 @pytest.mark.parametrize("S", [0, 1, 3])
 @pytest.mark.parametrize("wdt", [torch.bfloat16, torch.float32])
 def test_moe_combine_add_rmsnorm_bit_exact(ops, T, k, H, S, wdt):

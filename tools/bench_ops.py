@@ -211,6 +211,34 @@ def bench_norm(ops):
         out = torch.empty_like(x)
         us = timeit(lambda: ops.fused_add_rmsnorm(out, x, r, w, 1e-5))
         emit(op="fused_add_rmsnorm", T=T, H=H, us=round(us, 1), TBps=round(4 * T * H * 2 / us / 1e6, 2))
+    # the decode step's other row-norm kernels, at a 64-row batch, inside a graph
+    hs = torch.ops.hipserve
+    M, S = 64, 4
+    for N in (4096, 5376):
+        ws = torch.randn(S * M * N, device=DEV) * 0.5
+        r = torch.randn(M, N, device=DEV, dtype=torch.bfloat16)
+        w = (torch.rand(N, device=DEV) + 0.5).to(torch.bfloat16)
+        w2 = (torch.rand(N, device=DEV) + 0.5).to(torch.bfloat16)
+        out = torch.empty_like(r)
+        table = torch.randn(32000, N, device=DEV, dtype=torch.bfloat16)
+        ids = torch.randint(0, 32000, (M,), device=DEV)
+        for name, fn in [
+            ("splitk_add_rmsnorm", lambda: hs.splitk_add_rmsnorm(out, r, ws, S, w, 1e-5)),
+            ("splitk_post_add_rmsnorm", lambda: hs.splitk_post_add_rmsnorm(out, r, ws, S, w, w2, 1e-5)),
+            ("embed_rmsnorm", lambda: hs.embed_rmsnorm(out, r, table, ids, None, None, w, 1e-5, 1.0)),
+        ]:
+            emit(op=name, M=M, N=N, S=S, us=round(graph_time(fn), 2))
+    T, k, H = 64, 8, 2048
+    cap = T * k + 64
+    slot = torch.randperm(cap, device=DEV)[: T * k].int()
+    tw = torch.rand(T, k, device=DEV)
+    r = torch.randn(T, H, device=DEV, dtype=torch.bfloat16)
+    nw = (torch.rand(H, device=DEV) + 0.5).to(torch.bfloat16)
+    out = torch.empty_like(r)
+    for S in (0, 4):  # bf16 expert rows, fp32 split-K partials
+        y = torch.randn(S, cap, H, device=DEV) if S else torch.randn(cap, H, device=DEV).to(torch.bfloat16)
+        us = graph_time(lambda: hs.moe_combine_add_rmsnorm(out, r, y, S, tw, slot, k, nw, 1e-6))
+        emit(op="moe_combine_add_rmsnorm", T=T, k=k, H=H, S=S, us=round(us, 2))
 
 
 def main():
