@@ -92,10 +92,15 @@ HS_DEVICE void qkv_sum8(float (&o)[8], const float* p, long slice, int S) {
 
 // two register sets for the chunk pipeline: keep VGPR + AGPR <= 256 so two waves fit
 // per SIMD (two 4-wave workgroups per CU — B = 64 x 8 kv heads is 2 per CU)
+// head_dim 256 (Gemma-3 1B / 4B / 12B): a register set is 128 registers (16 + 16 K quads,
+// 16 V quads), two sets + 64 accumulators + 32 Q registers are ~370 — over 256, and under that
+// cap the kernel spilled ~700 B / lane. Its plan is ONE wave per SIMD (4-wave workgroups only,
+// one per CU) on the unified 512-entry VGPR + AGPR file: the same two-set pipeline with no
+// scratch; each wave keeps a whole 32 KB chunk in flight, 128 KB per CU
 // KV: the cache element, bf16 (unsigned short) or e4m3 (unsigned char, widened to bf16
 // in registers right before its MFMA: half the HBM bytes of the memory-bound stream)
 template <int D, int kDecWaves, bool kQKV = false, bool kNT = true, typename KV = unsigned short>
-__global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(2, 8))) void paged_decode_kernel(
+__global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(D == 256 ? 1 : 2, 8))) void paged_decode_kernel(
     unsigned short* __restrict__ out, long out_stride,
     const unsigned short* __restrict__ q, long q_stride,
     const KV* __restrict__ k_cache,
@@ -104,11 +109,12 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
     const int* __restrict__ context_lens, float* __restrict__ tmp_out,
     float* __restrict__ tmp_ml, int nq, int nkv, int block_size, int part_size,
     int max_parts, float scale, int window, QkvIn qi = QkvIn{}, unsigned short* __restrict__ out16 = nullptr) {
-  static_assert(D == 128 || D == 96 || D == 64, "head_dim 64, 96 or 128");
+  static_assert(D == 256 || D == 128 || D == 96 || D == 64, "head_dim 64, 96, 128 or 256");
+  static_assert(D != 256 || (kDecWaves == 4 && !kQKV), "head_dim 256: one wave per SIMD, no fused qkv input");
   static_assert(!kQKV || sizeof(KV) == 2, "the fused qkv decode writes a bf16 cache");
   constexpr int KS = D / 32;  // k-steps of the QK MFMA
   constexpr int NB = D / 16;  // 16-column blocks of the PV output
-  // e4m3 cache (head_dim 64 / 128): 64-token chunks so every K / V load is 16 bytes (16 d
+  // e4m3 cache (head_dim 64 / 128 / 256): 64-token chunks so every K / V load is 16 bytes (16 d
   // of one key, 16 keys of one V^T row) — with 32-token chunks the e4m3 stream ran as
   // 8-byte loads at ~3.7 TB/s, issue- rather than HBM-bound. The QK MFMA's k index is
   // permuted to match: k-step ks, lane group g, slot j <-> d = 16 g + 64 (ks >> 1) + 8 (ks & 1) + j
@@ -644,7 +650,15 @@ static size_t smem_bytes(int D, int waves) {
          (size_t)(D / 32) * 64 * 16;
 }
 
-size_t paged_decode_smem_bytes(int D) { return smem_bytes(D, kDecWavesMax); }
+// head_dim 256 runs 4 waves only (the kernel's register plan): 75 KiB
+size_t paged_decode_smem_bytes(int D) { return smem_bytes(D, D == 256 ? 4 : kDecWavesMax); }
+
+// dynamic LDS above the 64 KiB default has to be allowed per kernel, once
+template <typename K>
+static bool big_lds(K* kernel, size_t bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)bytes) == hipSuccess;
+}
 
 // waves per workgroup (HIPSERVE_DECODE_WAVES = 4 | 8). 8 waves = more concurrent
 // 32-token chunk streams per (sequence, kv head) but measured no faster on
@@ -670,7 +684,7 @@ static bool decode_nt(long workgroups) {
 }
 
 // the decode kernel's chunk (= window-origin alignment): 64 keys for an e4m3 cache at head_dim
-// 64 / 128 (paged_decode_kernel kWide), else 32
+// 64 / 128 / 256 (paged_decode_kernel kWide), else 32
 static int dec_align(int D, bool kv_f8) { return kv_f8 && D != 96 ? 2 * kChunk : kChunk; }
 
 void launch_paged_decode(void* out, long out_stride, const void* q, long q_stride,
@@ -682,7 +696,7 @@ void launch_paged_decode(void* out, long out_stride, const void* q, long q_strid
                          hipStream_t s, void* out16, bool kv_f8) {
   if (B <= 0) return;
   auto* o16 = static_cast<unsigned short*>(out16);
-  const int waves = decode_waves();
+  const int waves = D == 256 ? 4 : decode_waves();
   dim3 grid(max_parts, nkv, B), block(64 * waves);
   const size_t smem = smem_bytes(D, waves);
   auto* o = static_cast<unsigned short*>(out);
@@ -693,6 +707,11 @@ void launch_paged_decode(void* out, long out_stride, const void* q, long q_strid
   auto* vc8 = static_cast<const unsigned char*>(v_cache);
 #define HS_DECODE_KV(DD, WW, NT)                                                                              \
   do {                                                                                                      \
+    if constexpr (DD == 256) { /* 75 KiB of merge LDS: above the 64 KiB default (160 KiB per CU) */         \
+      static const bool attr = big_lds(paged_decode_kernel<DD, WW, false, NT, unsigned char>, smem) &&      \
+                               big_lds(paged_decode_kernel<DD, WW, false, NT>, smem);                        \
+      (void)attr;                                                                                           \
+    }                                                                                                       \
     if (kv_f8)                                                                                              \
       paged_decode_kernel<DD, WW, false, NT, unsigned char><<<grid, block, smem, s>>>(                      \
           o, out_stride, qq, q_stride, kc8, vc8, block_tables, bt_stride, context_lens, tmp_out, tmp_ml, nq, \
@@ -718,7 +737,13 @@ void launch_paged_decode(void* out, long out_stride, const void* q, long q_strid
   } while (0)
   if (D == 128) HS_DECODE_D(128);
   else if (D == 96) HS_DECODE_D(96);
-  else HS_DECODE_D(64);
+  else if (D == 64) HS_DECODE_D(64);
+  else {  // 256: the one-wave-per-SIMD plan, 4 waves whatever HIPSERVE_DECODE_WAVES says
+    HS_DECODE(256, 4);
+    if (max_parts > 1)
+      paged_decode_reduce_kernel<256><<<dim3(nq, B), dim3(reduce_groups<256>() * 256), 0, s>>>(
+          o, out_stride, tmp_out, tmp_ml, context_lens, nq, part_size, max_parts, window, dec_align(256, kv_f8), o16);
+  }
 #undef HS_DECODE_D
 #undef HS_DECODE
 #undef HS_DECODE_KV

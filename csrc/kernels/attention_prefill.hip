@@ -524,7 +524,10 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
                                                                      block_tables, bt_stride, cu_q, ctx_lens,   \
                                                                      tiles, nq, nkv, block_size, scale, window); \
   } while (0)
-  if (D == 128) PA1_LAUNCH(128);
+  // head_dim 256 (Gemma-3 1B / 4B / 12B) runs v1: 256 VGPRs + the accumulators in AGPRs at one
+  // wave per SIMD, no scratch; a v2-class kernel there is a design of its own (README Limits)
+  if (D == 256) PA1_LAUNCH(256);
+  else if (D == 128) PA1_LAUNCH(128);
   else if (D == 96) PA1_LAUNCH(96);
   else PA1_LAUNCH(64);
 #undef PA1_LAUNCH

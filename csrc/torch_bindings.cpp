@@ -473,7 +473,7 @@ void paged_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& k_cach
   Args a("paged_decode", q, "q");
   const KvCache kv = kv_cache(a, k_cache, v_cache, nkv);
   const int D = kv.D;
-  TORCH_CHECK(D == 64 || D == 96 || D == 128, "paged_decode: head_dim 64/96/128");
+  TORCH_CHECK(D == 64 || D == 96 || D == 128 || D == 256, "paged_decode: head_dim 64/96/128/256");
   const void* qp = a.ptr(q, "q", BF16, ROWS, {ANY, at_least(nq * D)});
   const int B = q.size(0);
   void* op = a.ptr(out, "out", BF16, ROWS, {at_least(B), at_least(nq * D)});
@@ -519,7 +519,7 @@ void prefill_attention(at::Tensor& out, const at::Tensor& q, const at::Tensor& k
   Args a("prefill_attention", q, "q");
   const KvCache kv = kv_cache(a, k_cache, v_cache, nkv);
   const int D = kv.D;
-  TORCH_CHECK(D == 64 || D == 96 || D == 128, "prefill_attention: head_dim 64/96/128");
+  TORCH_CHECK(D == 64 || D == 96 || D == 128 || D == 256, "prefill_attention: head_dim 64/96/128/256");
   TORCH_CHECK(window >= 0, "prefill_attention: window >= 0");
   TORCH_CHECK(kv.bs % 16 == 0 && nq % nkv == 0, "prefill_attention: block_size % 16 == 0, nq % nkv == 0");
   const void* qp = a.ptr(q, "q", BF16, ROWS, {ANY, at_least(nq * D)});

@@ -273,6 +273,20 @@ def _rope_params(d: dict, layer_type: str | None) -> tuple[float, dict | None]:
 _LLAMA3_SCALING = {"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0,
                    "high_freq_factor": 4.0, "original_max_position_embeddings": 8192}
 
+def _gemma3(name: str, *, hidden_size: int, num_layers: int, sliding_window: int = 1024,
+            vocab_size: int = 262208, max_position_embeddings: int = 131072,
+            rope_scaling: dict | None = {"rope_type": "linear", "factor": 8.0}, **kw) -> ModelConfig:
+    """Gemma-3 1B / 4B / 12B text model: head_dim 256 = query_pre_attn_scalar, five sliding
+    layers (RoPE base 1e4) to one global layer (base 1e6, the linear scaling), tied embeddings."""
+    return ModelConfig(name=name, family="gemma3", hidden_size=hidden_size, num_layers=num_layers, head_dim=256,
+                       vocab_size=vocab_size, rms_norm_eps=1e-6, rope_theta=1e6, rope_scaling=rope_scaling,
+                       max_position_embeddings=max_position_embeddings, tie_word_embeddings=True, qk_norm=True,
+                       hidden_act="gelu_tanh", sandwich_norm=True, norm_offset=True,
+                       embed_scale=hidden_size ** 0.5, attn_scale=256 ** -0.5, sliding_window=sliding_window,
+                       layer_windows=tuple(sliding_window if (i + 1) % 6 else 0 for i in range(num_layers)),
+                       rope_local_theta=1e4, bos_token_id=2, eos_token_id=(1, 106), **kw)
+
+
 # Public architecture hyper-parameters (SURVEY §2.E). Random-init weights of these
 # shapes are what the benchmarks run (no network => no checkpoints).
 PRESETS: dict[str, ModelConfig] = {
@@ -326,6 +340,14 @@ PRESETS: dict[str, ModelConfig] = {
                                embed_scale=5376 ** 0.5, attn_scale=168 ** -0.5, sliding_window=1024,
                                layer_windows=tuple(1024 if (i + 1) % 6 else 0 for i in range(62)),
                                rope_local_theta=1e4, bos_token_id=2, eos_token_id=(1, 106)),
+    # the smaller Gemma-3 text models: head_dim 256 (the 27B alone has 128), published config.json values
+    "gemma-3-1b": _gemma3("gemma-3-1b", hidden_size=1152, num_layers=26, num_heads=4, num_kv_heads=1,
+                          intermediate_size=6912, sliding_window=512, max_position_embeddings=32768,
+                          vocab_size=262144, rope_scaling=None),
+    "gemma-3-4b": _gemma3("gemma-3-4b", hidden_size=2560, num_layers=34, num_heads=8, num_kv_heads=4,
+                          intermediate_size=10240),
+    "gemma-3-12b": _gemma3("gemma-3-12b", hidden_size=3840, num_layers=48, num_heads=16, num_kv_heads=8,
+                           intermediate_size=15360),
     "phi-3-mini": ModelConfig(name="phi-3-mini", family="phi3", hidden_size=3072, num_layers=32,
                               num_heads=32, num_kv_heads=32, head_dim=96, intermediate_size=8192,
                               vocab_size=32064, rope_theta=10000.0, max_position_embeddings=4096,

@@ -31,6 +31,7 @@ from .scheduler import SchedulerOutput
 log = logging.getLogger("hipserve.runner")
 PREFILL_TILE = 128
 TOP_LOGPROBS = 20   # per-row capacity of the device top-logprobs output (OpenAI max)
+GPU_HEAD_DIMS = (64, 96, 128, 256)  # head sizes of the paged decode / prefill attention kernels
 GRAPH_BUCKETS = [1, 2, 4, 8, 16, 24, 32, 48, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384, 448, 512]
 
 
@@ -99,6 +100,10 @@ class ModelRunner:
                       "float32": torch.float32, "fp32": torch.float32}[ecfg.dtype]
         if self.device.type == "cuda" and self.dtype != torch.bfloat16:
             raise ValueError("the gfx950 kernels run bf16 activations; use --dtype bfloat16")
+        if self.device.type == "cuda" and mcfg.head_dim not in GPU_HEAD_DIMS:
+            # here, not as a kernel's argument check on the first forward
+            raise ValueError(f"{mcfg.name}: head_dim {mcfg.head_dim} has no gfx950 attention kernel "
+                             f"(supported: {', '.join(map(str, GPU_HEAD_DIMS))})")
         self.ops = get_ops(self.device)
         self.max_model_len = min(ecfg.max_model_len or mcfg.max_position_embeddings,
                                  mcfg.max_position_embeddings)

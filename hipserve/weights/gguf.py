@@ -171,6 +171,9 @@ class GGUFFile:
         if md.get("tokenizer.ggml.eot_token_id") is not None:
             eos_ids.add(int(md["tokenizer.ggml.eot_token_id"]))
         n_exp = int(g("expert_count", 0) or 0)
+        if a in ("gemma", "gemma2"):
+            raise NotImplementedError(f"GGUF architecture {a!r}: Gemma-1 / Gemma-2 need logit soft-capping, which "
+                                      f"the decoder does not have (gemma3 is served)")
         if a not in GGUF_ARCHS:
             raise NotImplementedError(f"GGUF architecture {a!r} (supported: {', '.join(GGUF_ARCHS)})")
         if int(g("expert_shared_count", 0) or 0):
@@ -183,7 +186,26 @@ class GGUFFile:
         if int(g("rope.dimension_count", head_dim) or head_dim) != head_dim:
             raise NotImplementedError("partial rotary embeddings are not supported")
         fam = {"llama": "mixtral" if n_exp else "llama", "qwen3moe": "qwen3_moe"}.get(a, a)
+        extra = {}
+        if a == "gemma3":
+            # what the file does not carry comes from the architecture (llama.cpp's gemma3 graph):
+            # GeGLU, sandwich norms, q/k norm, every 6th layer global with the file's RoPE base and
+            # linear scaling, the others a sliding window on base 10000. Norm weights are stored
+            # with Gemma's + 1 already added (norm_offset: fp32 norms, load_gguf_weights adds nothing)
+            L, win = int(g("block_count")), int(g("attention.sliding_window", 0) or 0)
+            factor = float(g("rope.scaling.factor", 1.0) or 1.0)
+            styp = g("rope.scaling.type")
+            if styp not in (None, "none", "linear"):
+                raise NotImplementedError(f"{self.path}: gemma3 RoPE scaling {styp!r} (linear only)")
+            # no query_pre_attn_scalar in the file: head_dim, except the 27B geometry (hidden / heads)
+            qpas = H / nh if L == 62 else head_dim
+            extra = dict(hidden_act="gelu_tanh", sandwich_norm=True, norm_offset=True, embed_scale=float(H) ** 0.5,
+                         attn_scale=float(qpas) ** -0.5, sliding_window=win,
+                         layer_windows=tuple(win if (i + 1) % 6 else 0 for i in range(L)), rope_local_theta=10000.0,
+                         rope_scaling={"rope_type": "linear", "factor": factor}
+                         if styp == "linear" and factor != 1.0 else None)
         return ModelConfig(
+            **extra,
             name=name or md.get("general.name", os.path.basename(self.path)),
             architecture="mixtral" if n_exp else "llama", family=fam,
             hidden_size=H, num_layers=int(g("block_count")), num_heads=nh,
@@ -198,7 +220,7 @@ class GGUFFile:
             max_position_embeddings=int(g("context_length", 4096)),
             tie_word_embeddings="output.weight" not in self.tensors,
             num_experts=n_exp, num_experts_per_tok=int(g("expert_used_count", 0) or 0),
-            qkv_bias=a == "qwen2", qk_norm=a in ("qwen3", "qwen3moe"),  # norm_topk_prob: the default (True)
+            qkv_bias=a == "qwen2", qk_norm=a in ("qwen3", "qwen3moe", "gemma3"),  # norm_topk_prob: the default (True)
             bos_token_id=int(md.get("tokenizer.ggml.bos_token_id", 1)),
             eos_token_id=tuple(sorted(eos_ids)))
 
@@ -566,6 +588,8 @@ class GGUFTokenizer:
             eos.add(int(md["tokenizer.ggml.eot_token_id"]))
         self.eos_token_ids = tuple(sorted(eos))
         self.add_bos = bool(md.get("tokenizer.ggml.add_bos_token", True))
+        # SentencePiece dummy prefix ("▁" before the first piece); Gemma files turn it off
+        self.add_space_prefix = bool(md.get("tokenizer.ggml.add_space_prefix", True))
         self.bos_token = self.tokens[self.bos_token_id] if self.bos_token_id < len(self.tokens) else ""
         self.eos_token = self.tokens[min(self.eos_token_ids)] if self.eos_token_ids else ""
         self.chat_template = md.get("tokenizer.chat_template") or _DEFAULT_CHAT_TEMPLATE
@@ -636,7 +660,7 @@ class GGUFTokenizer:
             elif self.kind == "gpt2":
                 ids += self._bpe_encode(piece)
             else:
-                ids += self._spm_encode(piece, add_prefix=first)
+                ids += self._spm_encode(piece, add_prefix=first and self.add_space_prefix)
             first = False
         return ids
 
@@ -737,7 +761,7 @@ class GGUFTokenizer:
 # ------------------------------------------------------------------ loading
 # llama.cpp architectures the GGUF tier serves (the reference's GGUF chart runs
 # TinyLlama (llama) and Phi-3-mini (phi3): ramalama-models/helm-chart/values.yaml:3-19)
-GGUF_ARCHS = ("llama", "phi3", "qwen2", "qwen3", "qwen3moe")
+GGUF_ARCHS = ("llama", "phi3", "qwen2", "qwen3", "qwen3moe", "gemma3")
 
 
 def gguf_name_map(layer: int) -> dict:
@@ -769,7 +793,9 @@ def load_gguf_weights(model, path: str):
         return torch.from_numpy(np.ascontiguousarray(t)).to(device=dev, dtype=dt)
 
     def norm(name):
-        return torch.from_numpy(gf.tensor_f32(name).astype(np.float32)).to(device=dev, dtype=dt)
+        # Gemma files hold 1 + w: kept in fp32 as the safetensors loader keeps its (1 + w), nothing added
+        return torch.from_numpy(gf.tensor_f32(name).astype(np.float32)).to(
+            device=dev, dtype=torch.float32 if cfg.norm_offset else dt)
 
     # HIPSERVE_GGUF_Q23_NATIVE=0 (A/B): Q2_K / Q3_K tensors decoded by numpy and kept as bf16
     q23_native = os.environ.get("HIPSERVE_GGUF_Q23_NATIVE", "1") != "0"
@@ -871,9 +897,12 @@ def load_gguf_weights(model, path: str):
             lw.wd = matrix(n["down"])
         if cfg.qkv_bias:  # qwen2
             lw.bqkv = torch.cat([dense(p + f"attn_{x}.bias") for x in ("q", "k", "v")]).contiguous()
-        if cfg.qk_norm:  # qwen3
+        if cfg.qk_norm:  # qwen3, gemma3
             lw.q_norm = torch.from_numpy(gf.tensor_f32(p + "attn_q_norm.weight").astype(np.float32)).to(dev)
             lw.k_norm = torch.from_numpy(gf.tensor_f32(p + "attn_k_norm.weight").astype(np.float32)).to(dev)
+        if cfg.sandwich_norm:  # gemma3
+            lw.post_attn_norm = norm(p + "post_attention_norm.weight")
+            lw.post_ff_norm = norm(p + "post_ffw_norm.weight")
         model.layers.append(lw)
     from ..ops.quant import BY_KQT, QuantMoE, quant_linear
 

@@ -102,7 +102,7 @@ def bench_sample(ops):
 
 def bench_decode(ops):
     import os
-    D = 128
+    D = int(os.environ.get("BENCH_D", "128"))  # head_dim: 64 / 96 / 128 / 256
     parts = [int(x) for x in os.environ.get("DECODE_PARTS", "512").split(",")]
     bss = [int(x) for x in os.environ.get("DECODE_BS", "16").split(",")]  # KV block sizes
     shapes = [(64, 1152, 32, 8), (64, 1280, 32, 8), (256, 1152, 32, 8), (1, 4096, 32, 8), (64, 4096, 64, 8)]
@@ -135,16 +135,18 @@ def bench_decode(ops):
             ops.paged_decode(out, q, kcs[i], vcs[i], bt, cl, to, tm, nq, nkv, part, 1 / math.sqrt(D))
 
         us = timeit(call)
-        emit(op="paged_decode", kv="fp8" if f8 else "bf16", B=B, ctx=ctx, nq=nq, nkv=nkv, part=part, bs=bs, cold=ncopy > 1,
+        emit(op="paged_decode", D=D, kv="fp8" if f8 else "bf16", B=B, ctx=ctx, nq=nq, nkv=nkv, part=part, bs=bs, cold=ncopy > 1,
              nt=os.environ.get("HIPSERVE_DECODE_NT", "1"), us=round(us, 1), TBps=round(byts / us / 1e6, 2))
         del kcs, vcs
 
 
 def bench_prefill(ops):
-    D, bs = 128, 16
+    D, bs = int(os.environ.get("BENCH_D", "128")), 16  # head_dim 256 runs v1 whatever the version asked for
     shapes = [(1024, 8, 32, 8), (4096, 2, 32, 8), (8192, 1, 32, 8), (1024, 8, 8, 1)]
     if os.environ.get("BENCH_PREFILL_LONG"):
         shapes = [(1024, 8, 32, 8), (8192, 1, 32, 8), (32768, 1, 32, 8)]
+    if os.environ.get("PREFILL_SHAPES"):  # "SxNSEQxNQxNKV,..." e.g. 1024x8x16x4
+        shapes = [tuple(int(v) for v in sh.split("x")) for sh in os.environ["PREFILL_SHAPES"].split(",")]
     vers = os.environ.get("BENCH_PREFILL_VERS", "v2w4,v2w8,v1").split(",")
     for S, nseq, nq, nkv in shapes:
         mb = S // bs
@@ -164,7 +166,7 @@ def bench_prefill(ops):
             os.environ["HIPSERVE_PREFILL_ATTN_WAVES"] = "8" if ver == "v2w8" else "4"
             us = timeit(lambda: ops.prefill_attention(out, q, kc, vc, bt, cu, ctx, tiles, nq, nkv,
                                                       1 / math.sqrt(D)), n=10)
-            emit(op="prefill_attention", ver=ver, S=S, nseq=nseq, nq=nq, nkv=nkv, us=round(us, 1),
+            emit(op="prefill_attention", D=D, ver=ver, S=S, nseq=nseq, nq=nq, nkv=nkv, us=round(us, 1),
                  TFLOPs=round(flops / us / 1e6, 1))
         os.environ.pop("HIPSERVE_PREFILL_ATTN_V1", None)
 
