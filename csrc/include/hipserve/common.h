@@ -249,4 +249,16 @@ HS_DEVICE void sum_slices8(f32x4& lo, f32x4& hi, const float* __restrict__ p, lo
   }
 }
 
+// That sum rounded to bf16, as the unfused split-K reduce writes it, returned as fp32:
+// what every fused split-K epilogue (decode_fused.hip, the fused decode attention) starts from
+HS_DEVICE void sum8_bf16(float (&o)[8], const float* __restrict__ p, long slice, int S) {
+  f32x4 lo, hi;
+  sum_slices8(lo, hi, p, slice, S);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    o[j] = bf16_to_f32(f32_to_bf16(lo[j]));
+    o[j + 4] = bf16_to_f32(f32_to_bf16(hi[j]));
+  }
+}
+
 }  // namespace hipserve

@@ -19,8 +19,8 @@
 //    (normalised O + (max, sum)) go to a workspace reduced by a second kernel.
 // Grid dims are fixed by (B, nkv, max_partitions) so the launch is hipGraph
 // capturable for a batch-size bucket; partitions past a sequence's end exit.
-#include "hipserve/common.h"
 #include "hipserve/kernels.h"
+#include "hipserve/rope_kv.h"
 
 #include <cstdlib>
 
@@ -42,7 +42,9 @@ HS_DEVICE void store_o16(unsigned short* __restrict__ out16, long row_off, int e
 // bf16 q row. The kernel sums them, applies RoPE to q (and to the new token's k),
 // writes the new token's k / v into the paged cache and attends — replacing the
 // separate splitk_rope_cache launch of the fused decode layer. Rounding matches that
-// kernel exactly (bf16 after the sum, bf16 after RoPE).
+// kernel exactly (bf16 after the sum, bf16 after RoPE): the sum, the q/k norm and the cache
+// addresses are rope_kv.h's. The five rope_rot loops stay written out here: see
+// profiles/rope_kv_refactor.md, "Sites that kept their own text".
 struct QkvIn {
   const float* ws;        // partials [S, B, N], N = (nq + 2 nkv) * D
   long slice;             // B * N
@@ -57,38 +59,6 @@ struct QkvIn {
   const float* kw;        // rotate-half only; rounding as splitk_rope_cache (bf16 after the norm)
   float eps;
 };
-
-// per-head RMSNorm of 8 + 8 values (d and d + D/2 of one rotate-half chunk) whose
-// head spans lanes: the same sum order as splitk_rope_cache's kNorm branch (own x
-// terms, own y terms, then the chunk-xor partners), applied and rounded to bf16
-template <int D>
-HS_DEVICE void qk_norm_apply(float (&x)[8], float (&y)[8], float ss, const float* nw, int d0, float eps) {
-  const float inv = rsqrtf(ss / D + eps);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    x[j] = bf16_to_f32(f32_to_bf16(x[j] * inv * nw[d0 + j]));
-    y[j] = bf16_to_f32(f32_to_bf16(y[j] * inv * nw[D / 2 + d0 + j]));
-  }
-}
-HS_DEVICE float sumsq16(const float (&x)[8], const float (&y)[8]) {
-  float ss = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) ss += x[j] * x[j];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) s2 += y[j] * y[j];
-  return ss + s2;
-}
-
-// 8 consecutive partial sums over the S slices, rounded to bf16 (as splitk_rope_cache)
-HS_DEVICE void qkv_sum8(float (&o)[8], const float* p, long slice, int S) {
-  f32x4 lo, hi;
-  sum_slices8(lo, hi, p, slice, S);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    o[j] = bf16_to_f32(f32_to_bf16(lo[j]));
-    o[j + 4] = bf16_to_f32(f32_to_bf16(hi[j]));
-  }
-}
 
 // two register sets for the chunk pipeline: keep VGPR + AGPR <= 256 so two waves fit
 // per SIMD (two 4-wave workgroups per CU — B = 64 x 8 kv heads is 2 per CU)
@@ -255,29 +225,26 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
     const long slot = qi.slots[b];
     const int nch = (end - start + CH - 1) / CH;
     if (end == ctx && slot >= 0 && wave == (nch - 1) % kDecWaves) {
-      const long blk = slot / block_size;
-      const int off = (int)(slot % block_size);
+      const KvSlot sl = kv_slot(slot, block_size);
       const int nk_items = qi.mode == 0 ? half / 8 : D / 8;
       const int it = lane;
       if (it < nk_items + D / 8) {
         if (it >= nk_items) {  // v: transposed cache block (tokens contiguous per d)
           const int c8 = it - nk_items;
           float x[8];
-          qkv_sum8(x, wrow + (long)(nq + nkv) * D + (long)kh * D + c8 * 8, qi.slice, qi.S);
-          unsigned short* vc = qi.v_cache + (blk * nkv + kh) * (long)D * block_size + off;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) vc[(c8 * 8 + j) * block_size] = f32_to_bf16(x[j]);
+          sum8_bf16(x, wrow + (long)(nq + nkv) * D + (long)kh * D + c8 * 8, qi.slice, qi.S);
+          sl.store_v8(qi.v_cache, nkv, kh, D, c8 * 8, x);
         } else {
           const float* kr = wrow + (long)nq * D + (long)kh * D;
-          unsigned short* kc = qi.k_cache + ((blk * nkv + kh) * block_size + off) * (long)D;
+          unsigned short* kc = sl.k_row(qi.k_cache, nkv, kh, D);
           if (qi.mode == 0) {
             float x[8], y[8];
-            qkv_sum8(x, kr + it * 8, qi.slice, qi.S);
-            qkv_sum8(y, kr + half + it * 8, qi.slice, qi.S);
+            sum8_bf16(x, kr + it * 8, qi.slice, qi.S);
+            sum8_bf16(y, kr + half + it * 8, qi.slice, qi.S);
             if (qi.kw != nullptr) {  // lanes 0 .. D/16-1 hold the head's chunks: xor within them
               float ss = sumsq16(x, y);
               for (int o = nk_items / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-              qk_norm_apply<D>(x, y, ss, qi.kw, it * 8, qi.eps);
+              qk_norm_apply(x, y, ss, qi.kw, it * 8, D, qi.eps);
             }
             u16x8 va, vb;
 #pragma unroll
@@ -288,11 +255,11 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
               va[j] = f32_to_bf16(ra);
               vb[j] = f32_to_bf16(rb);
             }
-            *reinterpret_cast<u16x8*>(kc + it * 8) = va;
-            *reinterpret_cast<u16x8*>(kc + half + it * 8) = vb;
+            kv_store8(kc + it * 8, va);
+            kv_store8(kc + half + it * 8, vb);
           } else {
             float x[8];
-            qkv_sum8(x, kr + it * 8, qi.slice, qi.S);
+            sum8_bf16(x, kr + it * 8, qi.slice, qi.S);
             u16x8 v;
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
@@ -303,7 +270,7 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
               v[2 * p] = f32_to_bf16(ra);
               v[2 * p + 1] = f32_to_bf16(rb);
             }
-            *reinterpret_cast<u16x8*>(kc + it * 8) = v;
+            kv_store8(kc + it * 8, v);
           }
         }
       }
@@ -318,7 +285,7 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
     const int h = kh * G + col;
     auto q_frag = [&](int ks, float (&v)[8]) {
       if (col < G) {
-        qkv_sum8(v, wrow + (long)h * D + 8 * grp + 32 * ks, qi.slice, qi.S);
+        sum8_bf16(v, wrow + (long)h * D + 8 * grp + 32 * ks, qi.slice, qi.S);
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = 0.f;
@@ -350,7 +317,7 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
         ss += __shfl_xor(ss, 16, 64);
 #pragma unroll
         for (int ks = 0; ks < KS / 2; ++ks) {
-          qk_norm_apply<D>(x[ks], y[ks], ss, qi.qw, 8 * grp + 32 * ks, qi.eps);
+          qk_norm_apply(x[ks], y[ks], ss, qi.qw, 8 * grp + 32 * ks, D, qi.eps);
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             const int i = 8 * grp + 32 * ks + j;

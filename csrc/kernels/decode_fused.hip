@@ -13,6 +13,7 @@
 // Both round exactly where the unfused chain rounds (bf16 after the sum, bf16
 // residual), so the fused and unfused decode paths are bit-identical.
 #include "hipserve/kernels.h"
+#include "hipserve/rope_kv.h"
 #include "hipserve/row_norm.h"
 
 namespace hipserve {
@@ -22,18 +23,6 @@ HS_DEVICE void add_bias8(float (&x)[8], const unsigned short* __restrict__ b) {
   const u16x8 v = *reinterpret_cast<const u16x8*>(b);
 #pragma unroll
   for (int j = 0; j < 8; ++j) x[j] = bf16_to_f32(f32_to_bf16(x[j] + bf16_to_f32(v[j])));
-}
-
-// sum over S slices of 8 consecutive fp32 partials (batched loads, common.h),
-// rounded to bf16 like the unfused reduce output, returned as fp32
-HS_DEVICE void sum8_bf16(float (&o)[8], const float* __restrict__ p, long slice, int S) {
-  f32x4 lo, hi;
-  sum_slices8(lo, hi, p, slice, S);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    o[j] = bf16_to_f32(f32_to_bf16(lo[j]));
-    o[j + 4] = bf16_to_f32(f32_to_bf16(hi[j]));
-  }
 }
 
 template <int NT, int VPT, bool kWF32>
@@ -179,8 +168,7 @@ void launch_splitk_post_add_rmsnorm(void* out, void* residual, const float* ws, 
 // Family extras, bit-identical to the unfused chain (GEMM -> bias add -> qk_rmsnorm ->
 // rope_cache): bias (Qwen2: bf16 [N], added to the bf16-rounded sum and rounded
 // again) and per-head q/k RMSNorm (Qwen3: fp32 weights [D]; a head's lanes are
-// consecutive, its sum of squares is reduced in qk_rmsnorm_vec_kernel's order: each
-// lane's two chunks (d and d + D/2) are the kernel's first xor pair, then xor 4, 2, 1).
+// consecutive, its sum of squares is reduced in the one order rope_kv.h states).
 template <int kMode, bool kNorm, typename KV>
 __global__ __launch_bounds__(64) void splitk_rope_cache_kernel(
     unsigned short* __restrict__ qkv, long qkv_stride, const float* __restrict__ ws, int S,
@@ -202,8 +190,7 @@ __global__ __launch_bounds__(64) void splitk_rope_cache_kernel(
   const float* wrow = ws + (long)t * N;
   const float* cs = cos_sin + pos * D;
   unsigned short* row = qkv + t * qkv_stride;
-  const long blk = slot >= 0 ? slot / block_size : 0;
-  const int off = slot >= 0 ? (int)(slot % block_size) : 0;
+  const KvSlot sl = kv_slot(slot, block_size);
 
   if (it >= n_qk) {  // V: transposed cache block (tokens contiguous per d)
     if (slot < 0) return;
@@ -211,9 +198,7 @@ __global__ __launch_bounds__(64) void splitk_rope_cache_kernel(
     float x[8];
     sum8_bf16(x, wrow + (nq + nkv) * D + kh * D + c * 8, slice, S);
     if (bias != nullptr) add_bias8(x, bias + (nq + nkv) * D + kh * D + c * 8);
-    KV* vc = v_cache + (blk * nkv + kh) * (long)D * block_size + off;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) kv_store1(vc + (c * 8 + j) * block_size, f32_to_bf16(x[j]));
+    sl.store_v8(v_cache, nkv, kh, D, c * 8, x);
     return;
   }
   const int h = it / qk_chunks, c = it % qk_chunks;
@@ -227,35 +212,17 @@ __global__ __launch_bounds__(64) void splitk_rope_cache_kernel(
       add_bias8(y, bias + h * D + half + c * 8);
     }
     if constexpr (kNorm) {
-      float ss = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ss += x[j] * x[j];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s2 += y[j] * y[j];
-      ss += s2;
+      float ss = sumsq16(x, y);
       for (int o = qk_chunks / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-      const float inv = rsqrtf(ss / D + eps);
-      const float* nw = h < nq ? qw : kw;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        x[j] = bf16_to_f32(f32_to_bf16(x[j] * inv * nw[c * 8 + j]));
-        y[j] = bf16_to_f32(f32_to_bf16(y[j] * inv * nw[half + c * 8 + j]));
-      }
+      qk_norm_apply(x, y, ss, h < nq ? qw : kw, c * 8, D, eps);
     }
     u16x8 va, vb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float co = cs[c * 8 + j], si = cs[half + c * 8 + j];
-      float ra, rb;
-      rope_rot(x[j], y[j], co, si, ra, rb);
-      va[j] = f32_to_bf16(ra);
-      vb[j] = f32_to_bf16(rb);
-    }
+    rope_half8_bf16(va, vb, x, y, cs, c * 8, half);
     if (h < nq) {
       *reinterpret_cast<u16x8*>(row + h * D + c * 8) = va;
       *reinterpret_cast<u16x8*>(row + h * D + half + c * 8) = vb;
     } else {
-      KV* dst = k_cache + ((blk * nkv + (h - nq)) * block_size + off) * (long)D;
+      KV* dst = sl.k_row(k_cache, nkv, h - nq, D);
       kv_store8(dst + c * 8, va);
       kv_store8(dst + half + c * 8, vb);
     }
@@ -264,39 +231,10 @@ __global__ __launch_bounds__(64) void splitk_rope_cache_kernel(
     sum8_bf16(x, wrow + h * D + c * 8, slice, S);
     if (bias != nullptr) add_bias8(x, bias + h * D + c * 8);
     u16x8 v;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int i = c * 4 + p;
-      const float co = cs[i], si = cs[half + i];
-      float ra, rb;
-      rope_rot(x[2 * p], x[2 * p + 1], co, si, ra, rb);
-      v[2 * p] = f32_to_bf16(ra);
-      v[2 * p + 1] = f32_to_bf16(rb);
-    }
+    rope_pairs8_bf16(v, x, cs, c * 4, half);
     if (h < nq) *reinterpret_cast<u16x8*>(row + h * D + c * 8) = v;
-    else kv_store8(k_cache + ((blk * nkv + (h - nq)) * block_size + off) * (long)D + c * 8, v);
+    else kv_store8(sl.k_row(k_cache, nkv, h - nq, D) + c * 8, v);
   }
-}
-
-template <typename KV>
-static void splitk_rope_cache_t(unsigned short* q, long qkv_stride, const float* ws, int S, const long* positions,
-                                const long* slots, const float* cos_sin, KV* kc, KV* vc, int T, int nq, int nkv,
-                                int D, int block_size, int mode, hipStream_t s, const unsigned short* b,
-                                const float* qw, const float* kw, float eps) {
-  const int qk_chunks = mode == 0 ? D / 16 : D / 8;
-  const int items = (nq + nkv) * qk_chunks + nkv * (D / 8);
-  const dim3 grid(T, (items + 63) / 64);
-  if (mode == 0 && qw != nullptr)
-    splitk_rope_cache_kernel<0, true, KV><<<grid, 64, 0, s>>>(q, qkv_stride, ws, S, positions, slots, cos_sin, kc,
-                                                               vc, T, nq, nkv, D, block_size, b, qw, kw, eps);
-  else if (mode == 0)
-    splitk_rope_cache_kernel<0, false, KV><<<grid, 64, 0, s>>>(q, qkv_stride, ws, S, positions, slots, cos_sin, kc,
-                                                                vc, T, nq, nkv, D, block_size, b, nullptr, nullptr,
-                                                                eps);
-  else
-    splitk_rope_cache_kernel<1, false, KV><<<grid, 64, 0, s>>>(q, qkv_stride, ws, S, positions, slots, cos_sin, kc,
-                                                                vc, T, nq, nkv, D, block_size, b, nullptr, nullptr,
-                                                                eps);
 }
 
 void launch_splitk_rope_cache(void* qkv, long qkv_stride, const float* ws, int S, const long* positions,
@@ -304,14 +242,21 @@ void launch_splitk_rope_cache(void* qkv, long qkv_stride, const float* ws, int S
                               int nkv, int D, int block_size, int mode, hipStream_t s, const void* bias,
                               const float* qw, const float* kw, float eps, bool kv_f8) {
   if (T <= 0) return;
-  auto* q = static_cast<unsigned short*>(qkv);
-  auto* b = static_cast<const unsigned short*>(bias);
-  if (kv_f8)
-    splitk_rope_cache_t(q, qkv_stride, ws, S, positions, slots, cos_sin, static_cast<unsigned char*>(k_cache),
-                        static_cast<unsigned char*>(v_cache), T, nq, nkv, D, block_size, mode, s, b, qw, kw, eps);
-  else
-    splitk_rope_cache_t(q, qkv_stride, ws, S, positions, slots, cos_sin, static_cast<unsigned short*>(k_cache),
-                        static_cast<unsigned short*>(v_cache), T, nq, nkv, D, block_size, mode, s, b, qw, kw, eps);
+  const int qk_chunks = mode == 0 ? D / 16 : D / 8;
+  const int items = (nq + nkv) * qk_chunks + nkv * (D / 8);
+  const dim3 grid(T, (items + 63) / 64);
+  kv_dispatch(kv_f8, [&](auto* kv) {
+    using KV = std::remove_pointer_t<decltype(kv)>;
+    rope_mode_dispatch(mode, [&](auto m) {
+      bool_dispatch(m() == 0 && qw != nullptr, [&](auto norm) {
+        constexpr bool kNorm = m() == 0 && norm();  // the q/k norm is rotate-half only
+        splitk_rope_cache_kernel<m(), kNorm, KV><<<grid, 64, 0, s>>>(
+            static_cast<unsigned short*>(qkv), qkv_stride, ws, S, positions, slots, cos_sin,
+            static_cast<KV*>(k_cache), static_cast<KV*>(v_cache), T, nq, nkv, D, block_size,
+            static_cast<const unsigned short*>(bias), kNorm ? qw : nullptr, kNorm ? kw : nullptr, eps);
+      });
+    });
+  });
 }
 
 // GLU over the split-K partials of a merged [gate | up] projection in the plain

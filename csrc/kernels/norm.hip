@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void qk_rmsnorm_kernel(unsigned short* __restr
 
 // Vector form for D = 8 * LPH (64 / 128 / 256): LPH lanes per head, one 16-byte
 // load per lane, 64 / LPH heads per wave, the sum of squares reduced over the
-// head's lane group with xor shuffles.
+// head's lane group with xor shuffles: the order the fused q/k norms repeat (rope_kv.h).
 template <int LPH>
 __global__ __launch_bounds__(256) void qk_rmsnorm_vec_kernel(unsigned short* __restrict__ qkv, long stride,
                                                              const float* __restrict__ qw,

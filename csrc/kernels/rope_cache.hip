@@ -13,22 +13,10 @@
 // KV: cache element, bf16 (unsigned short) or e4m3 (unsigned char, common.h kv_store*).
 #include <cstdlib>
 
-#include "hipserve/common.h"
 #include "hipserve/kernels.h"
+#include "hipserve/rope_kv.h"
 
 namespace hipserve {
-
-template <int kMode>
-HS_DEVICE void rotate8(float (&x)[8], float (&y)[8], const float* cs, int i0,
-                       int half) {
-  // NeoX: x = elems [i0, i0+8) of the first half, y = same of the second half.
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float c = cs[i0 + j], s = cs[half + i0 + j];
-    const float a = x[j], b = y[j];
-    rope_rot(a, b, c, s, x[j], y[j]);
-  }
-}
 
 // One workgroup per token; threads stride over (head, 8-wide chunk) work items.
 template <int kMode, typename KV>
@@ -44,8 +32,7 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(
   const int half = D / 2;
   const float* cs = cos_sin + pos * D;
   unsigned short* row = qkv + t * qkv_stride;
-  const long blk = slot >= 0 ? slot / block_size : 0;
-  const int off = slot >= 0 ? (int)(slot % block_size) : 0;
+  const KvSlot sl = kv_slot(slot, block_size);
 
   if constexpr (kMode == 0) {
     // rotate-half: a work item = (head, chunk of 8 in the first half)
@@ -57,17 +44,14 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(
       u16x8 va = *reinterpret_cast<u16x8*>(base + c * 8);
       u16x8 vb = *reinterpret_cast<u16x8*>(base + half + c * 8);
       float x[8], y[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { x[j] = bf16_to_f32(va[j]); y[j] = bf16_to_f32(vb[j]); }
-      rotate8<0>(x, y, cs, c * 8, half);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { va[j] = f32_to_bf16(x[j]); vb[j] = f32_to_bf16(y[j]); }
+      bf16_unpack8(x, va);
+      bf16_unpack8(y, vb);
+      rope_half8_bf16(va, vb, x, y, cs, c * 8, half);
       if (h < nq) {
         *reinterpret_cast<u16x8*>(base + c * 8) = va;
         *reinterpret_cast<u16x8*>(base + half + c * 8) = vb;
       } else if (slot >= 0) {
-        const int kh = h - nq;
-        KV* kc = k_cache + ((blk * nkv + kh) * block_size + off) * (long)D;
+        KV* kc = sl.k_row(k_cache, nkv, h - nq, D);
         kv_store8(kc + c * 8, va);
         kv_store8(kc + half + c * 8, vb);
       }
@@ -79,24 +63,12 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(
     for (int it = threadIdx.x; it < items; it += blockDim.x) {
       const int h = it / chunks, c = it % chunks;
       unsigned short* base = row + h * D;
-      u16x8 v = *reinterpret_cast<u16x8*>(base + c * 8);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int i = c * 4 + p;  // pair index
-        const float co = cs[i], si = cs[half + i];
-        const float a = bf16_to_f32(v[2 * p]), b = bf16_to_f32(v[2 * p + 1]);
-        float ra, rb;
-        rope_rot(a, b, co, si, ra, rb);
-        v[2 * p] = f32_to_bf16(ra);
-        v[2 * p + 1] = f32_to_bf16(rb);
-      }
-      if (h < nq) {
-        *reinterpret_cast<u16x8*>(base + c * 8) = v;
-      } else if (slot >= 0) {
-        const int kh = h - nq;
-        KV* kc = k_cache + ((blk * nkv + kh) * block_size + off) * (long)D;
-        kv_store8(kc + c * 8, v);
-      }
+      float x[8];
+      bf16_unpack8(x, *reinterpret_cast<u16x8*>(base + c * 8));
+      u16x8 v;
+      rope_pairs8_bf16(v, x, cs, c * 4, half);
+      if (h < nq) *reinterpret_cast<u16x8*>(base + c * 8) = v;
+      else if (slot >= 0) kv_store8(sl.k_row(k_cache, nkv, h - nq, D) + c * 8, v);
     }
   }
   // V: copy to the transposed cache block (tokens contiguous per d).
@@ -105,10 +77,7 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(
     const int chunks = D / 8;
     for (int it = threadIdx.x; it < nkv * chunks; it += blockDim.x) {
       const int kh = it / chunks, c = it % chunks;
-      const u16x8 v = *reinterpret_cast<const u16x8*>(vrow + kh * D + c * 8);
-      KV* vc = v_cache + (blk * nkv + kh) * (long)D * block_size + off;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) kv_store1(vc + (c * 8 + j) * block_size, v[j]);
+      sl.store_v8(v_cache, nkv, kh, D, c * 8, *reinterpret_cast<const u16x8*>(vrow + kh * D + c * 8));
     }
   }
 }
@@ -142,12 +111,11 @@ __global__ __launch_bounds__(256) void rope_cache_tile_kernel(
     const long slot = slots[t];
     const float* cs = cos_sin + pos * D;
     unsigned short* row = qkv + t * qkv_stride;
-    const long blk = slot >= 0 ? slot / block_size : 0;
-    const int off = slot >= 0 ? (int)(slot % block_size) : 0;
+    const KvSlot sl = kv_slot(slot, block_size);
     if constexpr (kMode == 0) {
-      float co[8], si[8];
+      float cr[16];  // the chunk's [cos | sin]
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { co[j] = cs[c * 8 + j]; si[j] = cs[half + c * 8 + j]; }
+      for (int j = 0; j < 8; ++j) { cr[j] = cs[c * 8 + j]; cr[8 + j] = cs[half + c * 8 + j]; }
       // 4 heads per batch with all their loads issued first: the per-thread head
       // loop is otherwise one dependent memory round trip per head
       for (int h0 = hpar; h0 < nh; h0 += 8) {
@@ -162,27 +130,24 @@ __global__ __launch_bounds__(256) void rope_cache_tile_kernel(
         for (int q = 0; q < 4; ++q) {
           const int h = h0 + 2 * q;
           if (h >= nh || (h >= nq && slot < 0)) continue;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float ra, rb;
-            rope_rot(bf16_to_f32(va[q][j]), bf16_to_f32(vb[q][j]), co[j], si[j], ra, rb);
-            va[q][j] = f32_to_bf16(ra);
-            vb[q][j] = f32_to_bf16(rb);
-          }
+          float x[8], y[8];
+          bf16_unpack8(x, va[q]);
+          bf16_unpack8(y, vb[q]);
+          rope_half8_bf16(va[q], vb[q], x, y, cr, 0, 8);
           if (h < nq) {
             *reinterpret_cast<u16x8*>(row + h * D + c * 8) = va[q];
             *reinterpret_cast<u16x8*>(row + h * D + half + c * 8) = vb[q];
           } else {
-            KV* dst = k_cache + ((blk * nkv + (h - nq)) * block_size + off) * (long)D;
+            KV* dst = sl.k_row(k_cache, nkv, h - nq, D);
             kv_store8(dst + c * 8, va[q]);
             kv_store8(dst + half + c * 8, vb[q]);
           }
         }
       }
     } else {
-      float co[4], si[4];
+      float cr[8];  // the chunk's [cos | sin]
 #pragma unroll
-      for (int p = 0; p < 4; ++p) { co[p] = cs[c * 4 + p]; si[p] = cs[half + c * 4 + p]; }
+      for (int p = 0; p < 4; ++p) { cr[p] = cs[c * 4 + p]; cr[4 + p] = cs[half + c * 4 + p]; }
       for (int h0 = hpar; h0 < nh; h0 += 8) {
         u16x8 v[4];
 #pragma unroll
@@ -192,15 +157,11 @@ __global__ __launch_bounds__(256) void rope_cache_tile_kernel(
         for (int q = 0; q < 4; ++q) {
           const int h = h0 + 2 * q;
           if (h >= nh || (h >= nq && slot < 0)) continue;
-#pragma unroll
-          for (int p = 0; p < 4; ++p) {
-            float ra, rb;
-            rope_rot(bf16_to_f32(v[q][2 * p]), bf16_to_f32(v[q][2 * p + 1]), co[p], si[p], ra, rb);
-            v[q][2 * p] = f32_to_bf16(ra);
-            v[q][2 * p + 1] = f32_to_bf16(rb);
-          }
+          float x[8];
+          bf16_unpack8(x, v[q]);
+          rope_pairs8_bf16(v[q], x, cr, 0, 4);
           if (h < nq) *reinterpret_cast<u16x8*>(row + h * D + c * 8) = v[q];
-          else kv_store8(k_cache + ((blk * nkv + (h - nq)) * block_size + off) * (long)D + c * 8, v[q]);
+          else kv_store8(sl.k_row(k_cache, nkv, h - nq, D) + c * 8, v[q]);
         }
       }
     }
@@ -223,14 +184,14 @@ __global__ __launch_bounds__(256) void rope_cache_tile_kernel(
   bool contig = vfast && nt == kRopeTile && (block_size & 7) == 0 && (off0 & 7) == 0 && off0 + kRopeTile <= block_size;
   for (int i = 1; contig && i < kRopeTile; ++i) contig = slots[t0 + i] == s0 + i;  // block-uniform
   if (contig) {
-    const long blk = s0 / block_size;
+    const KvSlot sl{s0 / block_size, off0, block_size};  // the 16 tokens share a block
     for (int it = threadIdx.x; it < 2 * VW; it += blockDim.x) {
       const int r = it >> 1, hl = it & 1;
       const int kh = r / D, d = r % D;
       u16x8 v;
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = vs[(hl * 8 + j) * VR + r];
-      kv_store8(v_cache + (blk * nkv + kh) * (long)D * block_size + (long)d * block_size + off0 + hl * 8, v);
+      kv_store8(sl.v_col(v_cache, nkv, kh, D, d) + hl * 8, v);
     }
     return;
   }
@@ -238,11 +199,10 @@ __global__ __launch_bounds__(256) void rope_cache_tile_kernel(
   const int tt = threadIdx.x & (kRopeTile - 1);
   const long slot = tt < nt ? slots[t0 + tt] : -1;
   if (slot < 0) return;  // after the only barrier
-  const long blk = slot / block_size;
-  const int off = (int)(slot % block_size);
+  const KvSlot sl = kv_slot(slot, block_size);
   for (int r = threadIdx.x / kRopeTile; r < VW; r += blockDim.x / kRopeTile) {
     const int kh = r / D, d = r % D;
-    kv_store1(v_cache + (blk * nkv + kh) * (long)D * block_size + (long)d * block_size + off, vs[tt * VR + r]);
+    kv_store1(sl.v_col(v_cache, nkv, kh, D, d), vs[tt * VR + r]);
   }
 }
 
@@ -262,44 +222,32 @@ static int rope_vfast() {  // HIPSERVE_ROPE_VFAST=0: 2-byte V^T stores for every
   return on;
 }
 
-template <typename KV>
-static void rope_cache_t(unsigned short* q, long qkv_stride, const long* positions, const long* slots,
-                         const float* cos_sin, KV* kc, KV* vc, int T, int nq, int nkv, int D, int block_size,
-                         int mode, hipStream_t s) {
-  // prefill chunks: the tile kernel (one workgroup per 16 tokens) only once there are
-  // >= 128 of them; below that the per-token kernel's wider grid wins (tools/bench_rope.py:
-  // 256 tokens 6-7 vs 13-17 us, 1,024 tokens within +-2 us, 4,096 tokens 23-33 vs 32-51 us)
-  if (T >= 2048 && nkv * D <= 2048 && rope_tile_enabled()) {
-    const dim3 tg((T + kRopeTile - 1) / kRopeTile);
-    const size_t smem = (size_t)kRopeTile * (nkv * D + 8) * sizeof(unsigned short);
-    if (mode == 0)
-      rope_cache_tile_kernel<0, KV><<<tg, 256, smem, s>>>(q, qkv_stride, positions, slots, cos_sin, kc, vc, T, nq,
-                                                          nkv, D, block_size, rope_vfast());
-    else
-      rope_cache_tile_kernel<1, KV><<<tg, 256, smem, s>>>(q, qkv_stride, positions, slots, cos_sin, kc, vc, T, nq,
-                                                          nkv, D, block_size, rope_vfast());
-    return;
-  }
-  if (mode == 0)
-    rope_cache_kernel<0, KV><<<T, 256, 0, s>>>(q, qkv_stride, positions, slots, cos_sin, kc, vc, nq, nkv, D,
-                                               block_size);
-  else
-    rope_cache_kernel<1, KV><<<T, 256, 0, s>>>(q, qkv_stride, positions, slots, cos_sin, kc, vc, nq, nkv, D,
-                                               block_size);
-}
-
 void launch_rope_cache(void* qkv, long qkv_stride, const long* positions,
                        const long* slots, const float* cos_sin, void* k_cache,
                        void* v_cache, int T, int nq, int nkv, int D,
                        int block_size, int mode, hipStream_t s, bool kv_f8) {
   if (T <= 0) return;
   auto* q = static_cast<unsigned short*>(qkv);
-  if (kv_f8)
-    rope_cache_t(q, qkv_stride, positions, slots, cos_sin, static_cast<unsigned char*>(k_cache),
-                 static_cast<unsigned char*>(v_cache), T, nq, nkv, D, block_size, mode, s);
-  else
-    rope_cache_t(q, qkv_stride, positions, slots, cos_sin, static_cast<unsigned short*>(k_cache),
-                 static_cast<unsigned short*>(v_cache), T, nq, nkv, D, block_size, mode, s);
+  // prefill chunks: the tile kernel (one workgroup per 16 tokens) only once there are
+  // >= 128 of them; below that the per-token kernel's wider grid wins (tools/bench_rope.py:
+  // 256 tokens 6-7 vs 13-17 us, 1,024 tokens within +-2 us, 4,096 tokens 23-33 vs 32-51 us)
+  const bool tile = T >= 2048 && nkv * D <= 2048 && rope_tile_enabled();
+  kv_dispatch(kv_f8, [&](auto* kv) {
+    using KV = std::remove_pointer_t<decltype(kv)>;
+    auto* kc = static_cast<KV*>(k_cache);
+    auto* vc = static_cast<KV*>(v_cache);
+    rope_mode_dispatch(mode, [&](auto m) {
+      if (tile) {
+        const dim3 tg((T + kRopeTile - 1) / kRopeTile);
+        const size_t smem = (size_t)kRopeTile * (nkv * D + 8) * sizeof(unsigned short);
+        rope_cache_tile_kernel<m(), KV><<<tg, 256, smem, s>>>(q, qkv_stride, positions, slots, cos_sin, kc, vc, T,
+                                                              nq, nkv, D, block_size, rope_vfast());
+      } else {
+        rope_cache_kernel<m(), KV><<<T, 256, 0, s>>>(q, qkv_stride, positions, slots, cos_sin, kc, vc, nq, nkv, D,
+                                                     block_size);
+      }
+    });
+  });
 }
 
 }  // namespace hipserve

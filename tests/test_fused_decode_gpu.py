@@ -117,8 +117,8 @@ def test_splitk_post_add_rmsnorm_bit_exact(ops, N, M, S, wf32):
 
 @pytest.mark.parametrize("mode", [0, 1])
 @pytest.mark.parametrize("S", [1, 4])
-def test_splitk_rope_cache_bit_exact(ops, mode, S):
-    T, nq, nkv, D, bs = 23, 32, 8, 128, 16
+def test_splitk_rope_cache_bit_exact(ops, mode, S, shape=(23, 32, 8, 128)):
+    (T, nq, nkv, D), bs = shape, 16
     N = (nq + 2 * nkv) * D
     ws = _partials(S, T, N, 7 + S)
     h = ws[0].clone()
@@ -137,6 +137,13 @@ def test_splitk_rope_cache_bit_exact(ops, mode, S):
     torch.ops.hipserve.splitk_rope_cache(qkv2, ws.contiguous(), S, pos, slots, cs, kc2, vc2, nq, nkv, D, mode)
     assert torch.equal(qkv1[:, : nq * D], qkv2[:, : nq * D])
     assert torch.equal(kc1, kc2) and torch.equal(vc1, vc2)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("S", [1, 9])  # 9: past one batch of 8 slice loads (kSliceBatch)
+@pytest.mark.parametrize("D", [64, 96])
+def test_splitk_rope_cache_head_dims_bit_exact(ops, mode, S, D):
+    test_splitk_rope_cache_bit_exact(ops, mode, S, shape=(5, 4, 2, D))
 
 
 @pytest.mark.parametrize("M", [1, 16, 40, 64])
@@ -298,7 +305,7 @@ def test_fused_decode_forward_bit_exact(ops, choices, family="llama", qkv_attn=F
         gemm.TUNER.table.update(old)
 
 
-@pytest.mark.parametrize("S,part", [(1, 512), (4, 128), (2, 2048)])
+@pytest.mark.parametrize("S,part", [(1, 512), (4, 128), (2, 2048), (9, 512)])
 @pytest.mark.parametrize("D", [128, 64])
 def test_paged_decode_qkv_qk_norm_bit_exact(ops, S, part, D):
     """Qwen3's per-head q / k RMSNorm inside the fused decode attention == splitk_rope_cache
@@ -307,7 +314,7 @@ def test_paged_decode_qkv_qk_norm_bit_exact(ops, S, part, D):
 
 
 @pytest.mark.parametrize("mode", [0, 1])
-@pytest.mark.parametrize("S,part", [(1, 512), (4, 128), (3, 256)])
+@pytest.mark.parametrize("S,part", [(1, 512), (4, 128), (3, 256), (9, 512)])
 @pytest.mark.parametrize("D", [128, 64])
 def test_paged_decode_qkv_bit_exact(ops, mode, S, part, D, qk_norm=False):
     """Fused qkv partials -> RoPE + KV write + attention == splitk_rope_cache followed

@@ -63,13 +63,13 @@ def _caches(nblocks, nkv, bs, D, fill=True):
 @pytest.mark.parametrize("bs", [16, 32])
 @pytest.mark.parametrize("T,layout", [(37, "random"), (300, "random"), (300, "contig"), (1000, "contig"),
                                       (300, "aligned"), (2500, "random"), (2500, "contig"), (2100, "aligned")])
-def test_rope_cache(ops, mode, bs, T, layout):
+def test_rope_cache(ops, mode, bs, T, layout, heads=(32, 8, 128)):
     """Per-token kernel (T < 2048) and the 16-token tile kernel of prefill chunks
     (LDS-staged V, token-fastest V^T stores), scattered and contiguous slots
     (contig: a chunk starting mid-block; aligned: block-aligned, so whole tiles take the
     16-byte V^T store path), vs the fp32 oracle."""
     torch.manual_seed(1)
-    nq, nkv, D = 32, 8, 128
+    nq, nkv, D = heads
     qkv = torch.randn(T, (nq + 2 * nkv) * D + 64, device=DEV, dtype=torch.bfloat16)[:, : (nq + 2 * nkv) * D]
     pos = torch.randint(0, 4000, (T,), device=DEV)
     nblk = max(64, (T + 2 * bs) // bs + 1)
@@ -86,6 +86,15 @@ def test_rope_cache(ops, mode, bs, T, layout):
     _close(qkv[:, : nq * D], qkv_r[:, : nq * D], atol=2e-2, rtol=1e-2)
     _close(kc, kc_r, atol=2e-2, rtol=1e-2)
     _close(vc, vc_r, atol=0)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("T,layout", [(37, "random"), (2100, "aligned")])
+@pytest.mark.parametrize("D", [64, 96])
+def test_rope_cache_head_dims(ops, mode, T, layout, D):
+    """Both writers at head_dim 64 and 96 (6 chunks per half: no power of two), vs the
+    fp32 oracle with test_rope_cache's tolerances."""
+    test_rope_cache(ops, mode, 16, T, layout, heads=(8, 2, D))
 
 
 @pytest.mark.parametrize("nq,nkv,D", [(32, 8, 128), (64, 8, 128), (32, 32, 64), (32, 4, 64), (32, 32, 96)])

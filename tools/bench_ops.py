@@ -2,7 +2,7 @@
 """Micro-benchmarks of individual hipserve kernels on the GPU (HIP-event timing,
 median of N launches). Prints one JSON line per case.
 
-    python tools/bench_ops.py [sample|decode|prefill|gemm|norm|all]
+    python tools/bench_ops.py [sample|decode|prefill|gemm|norm|rope|all]
 """
 import json
 import math
@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from hipserve.ops import KernelOps  # noqa: E402
+from hipserve.ops import KernelOps, reference  # noqa: E402
 
 DEV = "cuda"
 
@@ -243,12 +243,49 @@ def bench_norm(ops):
         emit(op="moe_combine_add_rmsnorm", T=T, k=k, H=H, S=S, us=round(us, 2))
 
 
+def bench_rope(ops):
+    """The RoPE + KV-write family at the Llama-3-8B shapes, inside a graph: rope_cache (per-token
+    kernel at T = 64, tile kernel at T = 8192), the split-K epilogue and the fused decode attention."""
+    hs = torch.ops.hipserve
+    nq, nkv, D, bs, S = 32, 8, 128, 16, 4
+    N = (nq + 2 * nkv) * D
+    cs = reference.rope_cos_sin(D, 8192, 500000.0).to(DEV)
+    for T in (64, 8192):
+        nblk = T // bs + 2
+        qkv = torch.randn(T, N, device=DEV, dtype=torch.bfloat16)
+        pos = torch.arange(T, device=DEV)
+        slots = torch.arange(T, device=DEV) + bs
+        kc = torch.zeros(nblk, nkv, bs, D, device=DEV, dtype=torch.bfloat16)
+        vc = torch.zeros(nblk, nkv, D, bs, device=DEV, dtype=torch.bfloat16)
+        us = graph_time(lambda: ops.rope_cache(qkv, pos, slots, cs, kc, vc, nq, nkv, D, 0))
+        emit(op="rope_cache", T=T, us=round(us, 2))
+    B, ctx, part = 64, 1152, 512
+    nblk = ctx // bs
+    ws = torch.randn(S, B, N, device=DEV) * 0.5
+    qkv = torch.empty(B, N, device=DEV, dtype=torch.bfloat16)
+    kc = torch.randn(B * nblk, nkv, bs, D, device=DEV).to(torch.bfloat16)
+    vc = torch.randn(B * nblk, nkv, D, bs, device=DEV).to(torch.bfloat16)
+    bt = torch.randperm(B * nblk, device=DEV).int().view(B, nblk)
+    cl = torch.full((B,), ctx, device=DEV, dtype=torch.int32)
+    pos = (cl - 1).long()
+    slots = bt[:, -1].long() * bs + (ctx - 1) % bs
+    us = graph_time(lambda: hs.splitk_rope_cache(qkv, ws, S, pos, slots, cs, kc, vc, nq, nkv, D, 0))
+    emit(op="splitk_rope_cache", T=B, S=S, us=round(us, 2))
+    parts = math.ceil(ctx / part)
+    out = torch.empty(B, nq * D, device=DEV, dtype=torch.bfloat16)
+    tmp = torch.empty(B, nq, parts, D, device=DEV)
+    ml = torch.empty(B, nq, parts, 2, device=DEV)
+    us = graph_time(lambda: hs.paged_decode_qkv(out, ws, S, pos, slots, cs, kc, vc, bt, cl, tmp, ml, nq, nkv, part,
+                                                D ** -0.5, 0, 0, None, None, None, 1e-6))
+    emit(op="paged_decode_qkv", B=B, ctx=ctx, S=S, us=round(us, 2))
+
+
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     ops = KernelOps()
     for name, fn in [("sample", bench_sample), ("decode", bench_decode), ("prefill", bench_prefill),
                      ("prefill_chunked", bench_prefill_chunked),
-                     ("gemm", bench_gemm), ("norm", bench_norm)]:
+                     ("gemm", bench_gemm), ("norm", bench_norm), ("rope", bench_rope)]:
         if which in ("all", name):
             fn(ops)
 
