@@ -196,6 +196,22 @@ HS_DEVICE u16x8 gelu_mul8(const u16x8 g, const u16x8 u) {
   return o;
 }
 
+// Logit soft-capping (Gemma-2): cap * tanh(x / cap) as c - 2c / (exp2(a x) + 1) with
+// a = 2 log2(e) / cap on v_exp_f32 + v_rcp_f32 — five VALU per value. exp2 overflows to +inf
+// (rcp -> 0) and underflows to 0 (rcp(1) = 1), so the result saturates to exactly +-c
+// and is NaN only for a NaN input. The cancellation near 0 is an absolute error of
+// ~1e-7 c. The attention kernels fold the score scale into a and log2(e) into c.
+struct SoftCap {
+  float a, c;
+};
+HS_DEVICE SoftCap softcap_make(float cap, float in_scale, float out_scale) {
+  return SoftCap{2.f * 1.4426950408889634f * in_scale / cap, cap * out_scale};
+}
+HS_DEVICE float softcap_apply(float x, const SoftCap sc) {
+  const float t = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x * sc.a) + 1.f);
+  return __builtin_fmaf(-2.f * sc.c, t, sc.c);
+}
+
 // Bijective XCD-aware block remap (MI355X: 8 XCDs, blocks dealt round-robin).
 // Blocks that share operand panels end up on the same XCD's L2.
 HS_DEVICE int xcd_remap(int bid, int nwg) {

@@ -32,6 +32,8 @@ void launch_rope_cache(void* qkv, long qkv_stride, const long* positions,
                        int block_size, int mode, hipStream_t s, bool kv_f8 = false);
 
 // attention_decode.hip
+// softcap (all three attention launchers): > 0 caps the scores, softcap * tanh(q.k * scale /
+// softcap), before the causal / window / context masks (Gemma-2); 0 = off
 size_t paged_decode_smem_bytes(int D);
 // fused decode: qkv split-K partials [S, B, N] -> RoPE(q, k) + KV write + attention
 void launch_paged_decode_qkv(void* out, long out_stride, const float* ws, int S, int N, const long* positions,
@@ -39,7 +41,8 @@ void launch_paged_decode_qkv(void* out, long out_stride, const float* ws, int S,
                              const int* block_tables, int bt_stride, const int* context_lens, float* tmp_out,
                              float* tmp_ml, int B, int nq, int nkv, int D, int block_size, int part_size,
                              int max_parts, float scale, int window, hipStream_t s, void* out16 = nullptr,
-                             const float* qw = nullptr, const float* kw = nullptr, float eps = 1e-6f);
+                             const float* qw = nullptr, const float* kw = nullptr, float eps = 1e-6f,
+                             float softcap = 0.f);
 // out16 (optional): f16 pair-order copy of out for a quantised o-projection (out's row stride)
 void launch_paged_decode(void* out, long out_stride, const void* q, long q_stride,
                          const void* k_cache, const void* v_cache,
@@ -47,7 +50,7 @@ void launch_paged_decode(void* out, long out_stride, const void* q, long q_strid
                          const int* context_lens, float* tmp_out, float* tmp_ml,
                          int B, int nq, int nkv, int D, int block_size,
                          int part_size, int max_parts, float scale, int window,
-                         hipStream_t s, void* out16 = nullptr, bool kv_f8 = false);
+                         hipStream_t s, void* out16 = nullptr, bool kv_f8 = false, float softcap = 0.f);
 
 // attention_prefill.hip — window > 0: sliding-window attention (keys within
 // window - 1 positions before the query), 0 = full causal
@@ -56,7 +59,8 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
                               const void* v_cache, const int* block_tables,
                               int bt_stride, const int* cu_q, const int* ctx_lens,
                               const int* tiles, int ntiles, int nq, int nkv, int D,
-                              int block_size, float scale, int window, hipStream_t s, bool kv_f8 = false);
+                              int block_size, float scale, int window, hipStream_t s, bool kv_f8 = false,
+                              float softcap = 0.f);
 
 // sampling.hip
 // ws: fp32 workspace of sample_workspace_floats(rows, V) for the multi-CU path
@@ -78,6 +82,9 @@ void launch_penalty_apply(void* logits, bool is_bf16, long stride, int rows, int
 void launch_logit_bias_apply(void* logits, bool is_bf16, long stride, int rows, int V, const int* slot,
                              const int* ids, const float* vals, const int* n, int nslots, int width,
                              hipStream_t s);
+// logits[r][v] = cap * tanh(logits[r][v] / cap) in place for v < V (Gemma-2 final logit
+// soft-capping); columns past V are not touched
+void launch_logit_softcap(void* logits, bool is_bf16, long stride, int rows, int V, float cap, hipStream_t s);
 void launch_penalty_update(const long* tok, const int* slot, int n, int* counts, unsigned int* seen, int V,
                            hipStream_t s);
 void launch_penalty_init(int* counts, unsigned int* seen, int V, const int* slots, const int* off,

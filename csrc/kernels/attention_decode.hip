@@ -69,7 +69,10 @@ struct QkvIn {
 // scratch; each wave keeps a whole 32 KB chunk in flight, 128 KB per CU
 // KV: the cache element, bf16 (unsigned short) or e4m3 (unsigned char, widened to bf16
 // in registers right before its MFMA: half the HBM bytes of the memory-bound stream)
-template <int D, int kDecWaves, bool kQKV = false, bool kNT = true, typename KV = unsigned short>
+// kCap: logit soft-capping (Gemma-2), score = softcap * tanh(q.k * scale / softcap), applied to
+// the raw score BEFORE the window / context masks (a capped mask value would be a live
+// score of -softcap); its own instantiations, so the uncapped kernels are the code they were
+template <int D, int kDecWaves, bool kQKV = false, bool kNT = true, typename KV = unsigned short, bool kCap = false>
 __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(D == 256 ? 1 : 2, 8))) void paged_decode_kernel(
     unsigned short* __restrict__ out, long out_stride,
     const unsigned short* __restrict__ q, long q_stride,
@@ -78,7 +81,8 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
     const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ context_lens, float* __restrict__ tmp_out,
     float* __restrict__ tmp_ml, int nq, int nkv, int block_size, int part_size,
-    int max_parts, float scale, int window, QkvIn qi = QkvIn{}, unsigned short* __restrict__ out16 = nullptr) {
+    int max_parts, float scale, int window, QkvIn qi = QkvIn{}, unsigned short* __restrict__ out16 = nullptr,
+    float softcap = 0.f) {
   static_assert(D == 256 || D == 128 || D == 96 || D == 64, "head_dim 64, 96, 128 or 256");
   static_assert(D != 256 || (kDecWaves == 4 && !kQKV), "head_dim 256: one wave per SIMD, no fused qkv input");
   static_assert(!kQKV || sizeof(KV) == 2, "the fused qkv decode writes a bf16 cache");
@@ -363,6 +367,12 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
     for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(bf16x8, qsh[ks * 64 + lane]);
   }
   const float sl2 = scale * kLog2e;
+  // a raw q.k sum as a log2-domain score
+  [[maybe_unused]] const SoftCap cap = softcap_make(kCap ? softcap : 1.f, scale, kLog2e);
+  auto score = [&](float raw) -> float {
+    if constexpr (kCap) return softcap_apply(raw, cap);
+    else return raw * sl2;
+  };
   f32x4 o[NB];
 #pragma unroll
   for (int n = 0; n < NB; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -383,8 +393,8 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int t0 = cs + 8 * grp + r;
-      sc[r] = (t0 >= lo && t0 <= last_tok) ? sa[r] * sl2 : -1e30f;
-      sc[r + 4] = (t0 + 4 >= lo && t0 + 4 <= last_tok) ? sb[r] * sl2 : -1e30f;
+      sc[r] = (t0 >= lo && t0 <= last_tok) ? score(sa[r]) : -1e30f;
+      sc[r + 4] = (t0 + 4 >= lo && t0 + 4 <= last_tok) ? score(sb[r]) : -1e30f;
     }
 #pragma unroll
     for (int r = 0; r < 8; ++r) mx = fmaxf(mx, sc[r]);
@@ -437,7 +447,7 @@ __global__ __launch_bounds__(64 * kDecWaves) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int tk = cs + 16 * grp + 4 * t + r;
-        sc[4 * t + r] = (tk >= lo && tk <= last_tok) ? st[t][r] * sl2 : -1e30f;
+        sc[4 * t + r] = (tk >= lo && tk <= last_tok) ? score(st[t][r]) : -1e30f;
         mx = fmaxf(mx, sc[4 * t + r]);
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -660,7 +670,7 @@ void launch_paged_decode(void* out, long out_stride, const void* q, long q_strid
                          const int* context_lens, float* tmp_out, float* tmp_ml,
                          int B, int nq, int nkv, int D, int block_size,
                          int part_size, int max_parts, float scale, int window,
-                         hipStream_t s, void* out16, bool kv_f8) {
+                         hipStream_t s, void* out16, bool kv_f8, float softcap) {
   if (B <= 0) return;
   auto* o16 = static_cast<unsigned short*>(out16);
   const int waves = D == 256 ? 4 : decode_waves();
@@ -672,26 +682,31 @@ void launch_paged_decode(void* out, long out_stride, const void* q, long q_strid
   auto* vc = static_cast<const unsigned short*>(v_cache);
   auto* kc8 = static_cast<const unsigned char*>(k_cache);
   auto* vc8 = static_cast<const unsigned char*>(v_cache);
-#define HS_DECODE_KV(DD, WW, NT)                                                                              \
+#define HS_DECODE_KV(DD, WW, NT, CAP)                                                                         \
   do {                                                                                                      \
     if constexpr (DD == 256) { /* 75 KiB of merge LDS: above the 64 KiB default (160 KiB per CU) */         \
-      static const bool attr = big_lds(paged_decode_kernel<DD, WW, false, NT, unsigned char>, smem) &&      \
-                               big_lds(paged_decode_kernel<DD, WW, false, NT>, smem);                        \
+      static const bool attr = big_lds(paged_decode_kernel<DD, WW, false, NT, unsigned char, CAP>, smem) && \
+                               big_lds(paged_decode_kernel<DD, WW, false, NT, unsigned short, CAP>, smem);  \
       (void)attr;                                                                                           \
     }                                                                                                       \
     if (kv_f8)                                                                                              \
-      paged_decode_kernel<DD, WW, false, NT, unsigned char><<<grid, block, smem, s>>>(                      \
+      paged_decode_kernel<DD, WW, false, NT, unsigned char, CAP><<<grid, block, smem, s>>>(                 \
           o, out_stride, qq, q_stride, kc8, vc8, block_tables, bt_stride, context_lens, tmp_out, tmp_ml, nq, \
-          nkv, block_size, part_size, max_parts, scale, window, QkvIn{}, o16);                              \
+          nkv, block_size, part_size, max_parts, scale, window, QkvIn{}, o16, softcap);                     \
     else                                                                                                    \
-      paged_decode_kernel<DD, WW, false, NT><<<grid, block, smem, s>>>(                                     \
+      paged_decode_kernel<DD, WW, false, NT, unsigned short, CAP><<<grid, block, smem, s>>>(                \
           o, out_stride, qq, q_stride, kc, vc, block_tables, bt_stride, context_lens, tmp_out, tmp_ml, nq,  \
-          nkv, block_size, part_size, max_parts, scale, window, QkvIn{}, o16);                              \
+          nkv, block_size, part_size, max_parts, scale, window, QkvIn{}, o16, softcap);                     \
+  } while (0)
+#define HS_DECODE_NT(DD, WW, CAP)                                                                           \
+  do {                                                                                                      \
+    if (decode_nt((long)max_parts * nkv * B)) HS_DECODE_KV(DD, WW, true, CAP);                              \
+    else HS_DECODE_KV(DD, WW, false, CAP);                                                                  \
   } while (0)
 #define HS_DECODE(DD, WW)                                                                                   \
   do {                                                                                                      \
-    if (decode_nt((long)max_parts * nkv * B)) HS_DECODE_KV(DD, WW, true);                                   \
-    else HS_DECODE_KV(DD, WW, false);                                                                       \
+    if (softcap > 0.f) HS_DECODE_NT(DD, WW, true);                                                          \
+    else HS_DECODE_NT(DD, WW, false);                                                                       \
   } while (0)
 #define HS_DECODE_D(DD)                                                                                      \
   do {                                                                                                      \
@@ -713,6 +728,7 @@ void launch_paged_decode(void* out, long out_stride, const void* q, long q_strid
   }
 #undef HS_DECODE_D
 #undef HS_DECODE
+#undef HS_DECODE_NT
 #undef HS_DECODE_KV
 }
 
@@ -722,7 +738,7 @@ void launch_paged_decode_qkv(void* out, long out_stride, const float* ws, int S,
                              const int* block_tables, int bt_stride, const int* context_lens, float* tmp_out,
                              float* tmp_ml, int B, int nq, int nkv, int D, int block_size, int part_size,
                              int max_parts, float scale, int window, hipStream_t s, void* out16,
-                             const float* qw, const float* kw, float eps) {
+                             const float* qw, const float* kw, float eps, float softcap) {
   if (B <= 0) return;
   auto* o16 = static_cast<unsigned short*>(out16);
   const int waves = decode_waves();
@@ -732,16 +748,21 @@ void launch_paged_decode_qkv(void* out, long out_stride, const float* ws, int S,
   auto* kc = static_cast<unsigned short*>(k_cache);
   auto* vc = static_cast<unsigned short*>(v_cache);
   const QkvIn qi{ws, (long)B * N, S, N, positions, slots, cos_sin, kc, vc, mode, qw, kw, eps};
-#define HS_DECODE_QKV(DD, WW)                                                                                  \
+#define HS_DECODE_QKV_NT(DD, WW, CAP)                                                                         \
   do {                                                                                                        \
     if (decode_nt((long)max_parts * nkv * B))                                                                 \
-      paged_decode_kernel<DD, WW, true, true><<<grid, block, smem, s>>>(                                      \
+      paged_decode_kernel<DD, WW, true, true, unsigned short, CAP><<<grid, block, smem, s>>>(                 \
           o, out_stride, nullptr, 0, kc, vc, block_tables, bt_stride, context_lens, tmp_out, tmp_ml, nq, nkv, \
-          block_size, part_size, max_parts, scale, window, qi, o16);                                          \
+          block_size, part_size, max_parts, scale, window, qi, o16, softcap);                                 \
     else                                                                                                      \
-      paged_decode_kernel<DD, WW, true, false><<<grid, block, smem, s>>>(                                     \
+      paged_decode_kernel<DD, WW, true, false, unsigned short, CAP><<<grid, block, smem, s>>>(                \
           o, out_stride, nullptr, 0, kc, vc, block_tables, bt_stride, context_lens, tmp_out, tmp_ml, nq, nkv, \
-          block_size, part_size, max_parts, scale, window, qi, o16);                                          \
+          block_size, part_size, max_parts, scale, window, qi, o16, softcap);                                 \
+  } while (0)
+#define HS_DECODE_QKV(DD, WW)                                                                                 \
+  do {                                                                                                        \
+    if (softcap > 0.f) HS_DECODE_QKV_NT(DD, WW, true);                                                        \
+    else HS_DECODE_QKV_NT(DD, WW, false);                                                                     \
   } while (0)
 #define HS_DECODE_QKV_D(DD)                                                                                   \
   do {                                                                                                        \
@@ -756,6 +777,7 @@ void launch_paged_decode_qkv(void* out, long out_stride, const float* ws, int S,
   else HS_DECODE_QKV_D(64);
 #undef HS_DECODE_QKV_D
 #undef HS_DECODE_QKV
+#undef HS_DECODE_QKV_NT
 }
 
 }  // namespace hipserve

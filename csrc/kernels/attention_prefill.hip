@@ -40,7 +40,10 @@ HS_DEVICE float xor32_sum(float v) {
 
 typedef unsigned short u16x4v __attribute__((ext_vector_type(4)));
 
-template <int D, typename KV>
+// kCap (both kernels): logit soft-capping (Gemma-2), score = softcap * tanh(q.k * scale /
+// softcap) on the raw score BEFORE the causal / window masks (a capped -inf would be a live
+// score of -softcap); its own instantiations, so the uncapped kernels are the code they were
+template <int D, typename KV, bool kCap = false>
 __global__ __launch_bounds__(256) void prefill_attn_kernel(
     unsigned short* __restrict__ out, long out_stride,
     const unsigned short* __restrict__ q, long q_stride,
@@ -49,7 +52,7 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(
     const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
     const int* __restrict__ tiles, int nq, int nkv, int block_size,
-    float scale, int window) {
+    float scale, int window, float softcap = 0.f) {
   constexpr int KS = D / 16;   // k-steps of QK (K = 16 per MFMA)
   constexpr int NB = D / 32;   // 32-row d blocks of O^T
   const int seq = tiles[2 * blockIdx.x], r0 = tiles[2 * blockIdx.x + 1];
@@ -76,6 +79,7 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(
       qf[ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(qp + 16 * ks));
   }
   const float sl2 = scale * 1.4426950408889634f;
+  [[maybe_unused]] const SoftCap cap = softcap_make(kCap ? softcap : 1.f, scale, 1.4426950408889634f);
   f32x16 o[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb)
@@ -125,7 +129,10 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int kk = kbase + (r & 3) + 8 * (r >> 2) + 4 * half;
-      const float v = (kk <= pos && (window <= 0 || kk > pos - window)) ? st[r] * sl2 : -INFINITY;
+      float sv;  // the log2-domain score
+      if constexpr (kCap) sv = softcap_apply(st[r], cap);
+      else sv = st[r] * sl2;
+      const float v = (kk <= pos && (window <= 0 || kk > pos - window)) ? sv : -INFINITY;
       st[r] = v;
       mx = fmaxf(mx, v);
     }
@@ -204,13 +211,13 @@ constexpr int PA2_KT = 64, PA2_KLD = 128 + 8, PA2_VLD = 64 + 8;
 // 256 of two waves per SIMD and spilled: 1.4-1.5x slower, profiles/r5_prefill_attn_bench.log.)
 // KV: cache element, bf16 or e4m3; e4m3 pieces (8 bytes) are widened to bf16 on their way
 // into the LDS ring, so the MFMA / softmax body is the same for both
-template <int HG, int NWV, typename KV>
+template <int HG, int NWV, typename KV, bool kCap = false>
 __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
     unsigned short* __restrict__ out, long out_stride, const unsigned short* __restrict__ q, long q_stride,
     const KV* __restrict__ k_cache, const KV* __restrict__ v_cache,
     const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ cu_q,
     const int* __restrict__ ctx_lens, const int* __restrict__ tiles, int nq, int nkv, int block_size,
-    float scale, int window, int prio) {
+    float scale, int window, int prio, float softcap = 0.f) {
   constexpr int D = 128, KS = 8, NB = 4;
   constexpr int RB = NWV / HG, QR = 32 * RB, SUB = 128 / QR;
   constexpr int NT = 64 * NWV, NP = 1024 / NT;  // threads; K (and V^T) 16-byte pieces per thread
@@ -303,6 +310,7 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
       qf[ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(qp + 16 * ks));
   }
   const float sl2 = scale * 1.4426950408889634f;
+  [[maybe_unused]] const SoftCap cap = softcap_make(kCap ? softcap : 1.f, scale, 1.4426950408889634f);
   f32x16 o[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb)
@@ -340,6 +348,14 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
         __builtin_amdgcn_sched_barrier(0);
       }
       if (prio) __builtin_amdgcn_s_setprio(0);
+      // soft-capping: st becomes the capped log2-domain score here, ahead of the masks, so
+      // the running max and the exponent below are of the capped score (no sl2 factor)
+      if constexpr (kCap) {
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) st[h2][r] = softcap_apply(st[h2][r], cap);
+      }
       // diagonal tile (causal mask) or a tile crossing some row's window start
       // (key offsets inside the tile are compile-time per accumulator slot: one compare +
       // select per score against the lane's limit, the window test only when one is set)
@@ -368,7 +384,7 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[h2][r]);
       mx = xor32_max(mx);
-      const float m_new = fmaxf(m_run, mx * sl2);
+      const float m_new = fmaxf(m_run, kCap ? mx : mx * sl2);
       // deferred rescale: the running max is kept while no row's max grew by more than
       // 8 (log2 units), so P = exp2(s - m_run) stays <= 256 (exact enough in bf16 / fp32;
       // O and l always share m_run) and the 64-accumulator rescale runs on few tiles
@@ -387,7 +403,9 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
         bf16x8 pb[2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float p = __builtin_amdgcn_exp2f(fmaf(st[h2][r], sl2, -m_run));
+          float p;
+          if constexpr (kCap) p = __builtin_amdgcn_exp2f(st[h2][r] - m_run);
+          else p = __builtin_amdgcn_exp2f(fmaf(st[h2][r], sl2, -m_run));
           ps[r & 3] += p;
           pb[r >> 3][r & 7] = static_cast<__bf16>(p);
         }
@@ -452,7 +470,7 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
                               const void* v_cache, const int* block_tables,
                               int bt_stride, const int* cu_q, const int* ctx_lens,
                               const int* tiles, int ntiles, int nq, int nkv, int D,
-                              int block_size, float scale, int window, hipStream_t s, bool kv_f8) {
+                              int block_size, float scale, int window, hipStream_t s, bool kv_f8, float softcap) {
   if (ntiles <= 0) return;
   const int G = nq / nkv;
   // v2 keeps the sequence's block ids in LDS next to its 70 KiB K / V ring (160 KiB per CU)
@@ -478,22 +496,26 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
     auto* v28 = static_cast<const unsigned char*>(v_cache);
     // block ids of one sequence (the per-workgroup key range is at most this) in dynamic LDS
     const size_t bt_lds = (size_t)bt_stride * sizeof(int);
-#define PA2_LAUNCH_KV(hg, nw, KVT, KP, VP)                                                                   \
+#define PA2_LAUNCH_KV(hg, nw, KVT, KP, VP, CAP)                                                              \
   do {                                                                                                      \
     static bool attr = [] { /* static 70 KiB + the block ids: above the 64 KiB default (160 KiB per CU) */ \
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_attn_v2_kernel<hg, nw, KVT>),       \
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_attn_v2_kernel<hg, nw, KVT, CAP>),  \
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;      \
     }();                                                                                                    \
     (void)attr;                                                                                             \
-    prefill_attn_v2_kernel<hg, nw, KVT><<<g2, 64 * nw, bt_lds, s>>>(o2, out_stride, q2, q_stride, KP, VP,    \
-                                                                    block_tables, bt_stride, cu_q, ctx_lens, \
-                                                                    tiles, nq, nkv, block_size, scale, window, \
-                                                                    prio);                                  \
+    prefill_attn_v2_kernel<hg, nw, KVT, CAP><<<g2, 64 * nw, bt_lds, s>>>(                                   \
+        o2, out_stride, q2, q_stride, KP, VP, block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,      \
+        block_size, scale, window, prio, softcap);                                                          \
+  } while (0)
+#define PA2_LAUNCH_CAP(hg, nw, CAP)                                                                         \
+  do {                                                                                                      \
+    if (kv_f8) PA2_LAUNCH_KV(hg, nw, unsigned char, k28, v28, CAP);                                        \
+    else PA2_LAUNCH_KV(hg, nw, unsigned short, k2, v2, CAP);                                                \
   } while (0)
 #define PA2_LAUNCH(hg, nw)                                                                                  \
   do {                                                                                                      \
-    if (kv_f8) PA2_LAUNCH_KV(hg, nw, unsigned char, k28, v28);                                             \
-    else PA2_LAUNCH_KV(hg, nw, unsigned short, k2, v2);                                                     \
+    if (softcap > 0.f) PA2_LAUNCH_CAP(hg, nw, true);                                                        \
+    else PA2_LAUNCH_CAP(hg, nw, false);                                                                     \
   } while (0)
     if (nwv == 8) {
       if (HG == 8) PA2_LAUNCH(8, 8);
@@ -504,6 +526,7 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
       else PA2_LAUNCH(2, 4);
     }
 #undef PA2_LAUNCH
+#undef PA2_LAUNCH_CAP
 #undef PA2_LAUNCH_KV
     return;
   }
@@ -512,17 +535,22 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
   auto* qq = static_cast<const unsigned short*>(q);
   auto* kc = static_cast<const unsigned short*>(k_cache);
   auto* vc = static_cast<const unsigned short*>(v_cache);
-#define PA1_LAUNCH(dd)                                                                                          \
+#define PA1_LAUNCH_CAP(dd, CAP)                                                                                 \
   do {                                                                                                          \
     if (kv_f8)                                                                                                  \
-      prefill_attn_kernel<dd, unsigned char><<<grid, block, 0, s>>>(                                            \
+      prefill_attn_kernel<dd, unsigned char, CAP><<<grid, block, 0, s>>>(                                       \
           o, out_stride, qq, q_stride, static_cast<const unsigned char*>(k_cache),                              \
           static_cast<const unsigned char*>(v_cache), block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,  \
-          block_size, scale, window);                                                                           \
+          block_size, scale, window, softcap);                                                                  \
     else                                                                                                        \
-      prefill_attn_kernel<dd, unsigned short><<<grid, block, 0, s>>>(o, out_stride, qq, q_stride, kc, vc,        \
-                                                                     block_tables, bt_stride, cu_q, ctx_lens,   \
-                                                                     tiles, nq, nkv, block_size, scale, window); \
+      prefill_attn_kernel<dd, unsigned short, CAP><<<grid, block, 0, s>>>(                                      \
+          o, out_stride, qq, q_stride, kc, vc, block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,         \
+          block_size, scale, window, softcap);                                                                  \
+  } while (0)
+#define PA1_LAUNCH(dd)                                                                                          \
+  do {                                                                                                          \
+    if (softcap > 0.f) PA1_LAUNCH_CAP(dd, true);                                                                \
+    else PA1_LAUNCH_CAP(dd, false);                                                                             \
   } while (0)
   // head_dim 256 (Gemma-3 1B / 4B / 12B) runs v1: 256 VGPRs + the accumulators in AGPRs at one
   // wave per SIMD, no scratch; a v2-class kernel there is a design of its own (README Limits)
@@ -531,6 +559,7 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
   else if (D == 96) PA1_LAUNCH(96);
   else PA1_LAUNCH(64);
 #undef PA1_LAUNCH
+#undef PA1_LAUNCH_CAP
 }
 
 }  // namespace hipserve

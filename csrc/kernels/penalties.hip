@@ -13,6 +13,8 @@
 //   logit_bias_apply  OpenAI logit_bias from its own per-sequence slot table (ids, biases,
 //                   count), added to the logits in place BEFORE the penalties (vLLM's
 //                   order) and after top_logprobs
+//   logit_softcap   Gemma-2 final logit soft-capping, cap * tanh(l / cap) in place: the model's
+//                   last step, ahead of everything above and below that reads the logits
 //   penalty_apply   logits rows in place, rows with slot < 0 untouched
 //   penalty_update  count the tokens sampled this step (after the sampler)
 //   top_logprobs    per row with n > 0: n largest log-softmax entries (radix
@@ -63,6 +65,22 @@ __global__ __launch_bounds__(256) void penalty_apply_kernel(T* __restrict__ logi
     const int c = cnt[v];
     l -= fp * (float)c + (c > 0 ? pp : 0.f);
     st_logit(row, v, l);
+  }
+}
+
+// grid (ceil(V / (256*8)), rows): 8 consecutive vocab entries per thread, element-wise
+// loads / stores (any V, any row alignment); fp32 math, one rounding to the logits' dtype
+template <typename T>
+__global__ __launch_bounds__(256) void logit_softcap_kernel(T* __restrict__ logits, long stride, int V, float cap) {
+  const int v0 = (blockIdx.x * 256 + threadIdx.x) * 8;
+  if (v0 >= V) return;
+  T* row = logits + (long)blockIdx.y * stride;
+  const SoftCap sc = softcap_make(cap, 1.f, 1.f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int v = v0 + e;
+    if (v >= V) break;
+    st_logit(row, v, softcap_apply(ld_logit(row, v), sc));
   }
 }
 
@@ -268,6 +286,15 @@ void launch_penalty_apply(void* logits, bool is_bf16, long stride, int rows, int
   else
     penalty_apply_kernel<float><<<grid, 256, 0, s>>>(static_cast<float*>(logits), stride, V, slot, pres, freq, rep,
                                                      counts, seen, words);
+}
+
+void launch_logit_softcap(void* logits, bool is_bf16, long stride, int rows, int V, float cap, hipStream_t s) {
+  if (rows <= 0 || V <= 0) return;
+  const dim3 grid((V + 256 * 8 - 1) / (256 * 8), rows);
+  if (is_bf16)
+    logit_softcap_kernel<unsigned short><<<grid, 256, 0, s>>>(static_cast<unsigned short*>(logits), stride, V, cap);
+  else
+    logit_softcap_kernel<float><<<grid, 256, 0, s>>>(static_cast<float*>(logits), stride, V, cap);
 }
 
 void launch_logit_bias_apply(void* logits, bool is_bf16, long stride, int rows, int V, const int* slot,

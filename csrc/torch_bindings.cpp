@@ -469,11 +469,12 @@ void paged_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& k_cach
                   const at::Tensor& v_cache, const at::Tensor& block_tables,
                   const at::Tensor& context_lens, at::Tensor& tmp_out, at::Tensor& tmp_ml,
                   int64_t nq, int64_t nkv, int64_t part_size, double scale, int64_t window,
-                  const c10::optional<at::Tensor>& out16) {
+                  const c10::optional<at::Tensor>& out16, double softcap) {
   Args a("paged_decode", q, "q");
   const KvCache kv = kv_cache(a, k_cache, v_cache, nkv);
   const int D = kv.D;
   TORCH_CHECK(D == 64 || D == 96 || D == 128 || D == 256, "paged_decode: head_dim 64/96/128/256");
+  TORCH_CHECK(softcap >= 0, "paged_decode: softcap >= 0 (0 = off)");
   const void* qp = a.ptr(q, "q", BF16, ROWS, {ANY, at_least(nq * D)});
   const int B = q.size(0);
   void* op = a.ptr(out, "out", BF16, ROWS, {at_least(B), at_least(nq * D)});
@@ -481,7 +482,8 @@ void paged_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& k_cach
                                         part_size, window);
   hipserve::launch_paged_decode(op, out.stride(0), qp, q.stride(0), kv.k, kv.v, g.block_tables, g.bt_stride,
                                 g.context_lens, g.tmp_out, g.tmp_ml, B, nq, nkv, D, kv.bs, part_size, g.max_parts,
-                                (float)scale, (int)window, cur_stream(), out16_arg(a, out16, out), kv.f8);
+                                (float)scale, (int)window, cur_stream(), out16_arg(a, out16, out), kv.f8,
+                                (float)softcap);
 }
 
 void paged_decode_qkv(at::Tensor& out, const at::Tensor& ws, int64_t splits, const at::Tensor& positions,
@@ -489,13 +491,14 @@ void paged_decode_qkv(at::Tensor& out, const at::Tensor& ws, int64_t splits, con
                       const at::Tensor& block_tables, const at::Tensor& context_lens, at::Tensor& tmp_out,
                       at::Tensor& tmp_ml, int64_t nq, int64_t nkv, int64_t part_size, double scale, int64_t window,
                       int64_t mode, const c10::optional<at::Tensor>& out16, const c10::optional<at::Tensor>& q_w,
-                      const c10::optional<at::Tensor>& k_w, double eps) {
+                      const c10::optional<at::Tensor>& k_w, double eps, double softcap) {
   Args a("paged_decode_qkv", ws, "ws");
   const KvCache kv = kv_cache(a, k_cache, v_cache, nkv);
   const int D = kv.D;
   TORCH_CHECK(!kv.f8, "paged_decode_qkv: bf16 KV cache only");
   TORCH_CHECK(D == 64 || D == 128, "paged_decode_qkv: head_dim 64/128");
   TORCH_CHECK(mode == 0 || mode == 1, "paged_decode_qkv: mode 0 / 1");
+  TORCH_CHECK(softcap >= 0, "paged_decode_qkv: softcap >= 0 (0 = off)");
   const float *qwp, *kwp;  // per-head q / k RMSNorm before RoPE (Qwen3)
   if (qk_norm_weights(a, q_w, k_w, D, &qwp, &kwp))
     TORCH_CHECK(mode == 0, "paged_decode_qkv: q/k norm needs rotate-half RoPE (mode 0)");
@@ -509,18 +512,20 @@ void paged_decode_qkv(at::Tensor& out, const at::Tensor& ws, int64_t splits, con
   hipserve::launch_paged_decode_qkv(op, out.stride(0), wsp, splits, N, r.positions, r.slots, r.cos_sin, mode, kv.k,
                                     kv.v, g.block_tables, g.bt_stride, g.context_lens, g.tmp_out, g.tmp_ml, B, nq,
                                     nkv, D, kv.bs, part_size, g.max_parts, (float)scale, (int)window, cur_stream(),
-                                    out16_arg(a, out16, out), qwp, kwp, (float)eps);
+                                    out16_arg(a, out16, out), qwp, kwp, (float)eps, (float)softcap);
 }
 
 void prefill_attention(at::Tensor& out, const at::Tensor& q, const at::Tensor& k_cache,
                        const at::Tensor& v_cache, const at::Tensor& block_tables,
                        const at::Tensor& cu_q, const at::Tensor& ctx_lens,
-                       const at::Tensor& tiles, int64_t nq, int64_t nkv, double scale, int64_t window) {
+                       const at::Tensor& tiles, int64_t nq, int64_t nkv, double scale, int64_t window,
+                       double softcap) {
   Args a("prefill_attention", q, "q");
   const KvCache kv = kv_cache(a, k_cache, v_cache, nkv);
   const int D = kv.D;
   TORCH_CHECK(D == 64 || D == 96 || D == 128 || D == 256, "prefill_attention: head_dim 64/96/128/256");
   TORCH_CHECK(window >= 0, "prefill_attention: window >= 0");
+  TORCH_CHECK(softcap >= 0, "prefill_attention: softcap >= 0 (0 = off)");
   TORCH_CHECK(kv.bs % 16 == 0 && nq % nkv == 0, "prefill_attention: block_size % 16 == 0, nq % nkv == 0");
   const void* qp = a.ptr(q, "q", BF16, ROWS, {ANY, at_least(nq * D)});
   void* op = a.ptr(out, "out", BF16, ROWS, {ANY, at_least(nq * D)});
@@ -530,7 +535,7 @@ void prefill_attention(at::Tensor& out, const at::Tensor& q, const at::Tensor& k
   const int* tp = a.as<int>(tiles, "tiles", CONTIG, {ANY, 2});
   hipserve::launch_prefill_attention(op, out.stride(0), qp, q.stride(0), kv.k, kv.v, bt, block_tables.stride(0), cu, cl,
                                      tp, tiles.size(0), nq, nkv, D, kv.bs, (float)scale, (int)window, cur_stream(),
-                                     kv.f8);
+                                     kv.f8, (float)softcap);
 }
 
 // Per-head RMSNorm of q and k inside the merged qkv rows, in place (Qwen3 / Gemma-3).
@@ -830,6 +835,14 @@ void penalty_apply(at::Tensor& logits, const at::Tensor& slot, const at::Tensor&
   hipserve::launch_penalty_apply(L.p, L.bf16, L.stride, L.rows, L.V, a.as<int>(slot, "slot", CONTIG, L.rows),
                                  a.as<float>(pres, "pres", CONTIG, L.rows), a.as<float>(freq, "freq", CONTIG, L.rows),
                                  a.as<float>(rep, "rep", CONTIG, L.rows), p.counts, p.seen, cur_stream());
+}
+
+// logits[:, :V] = cap * tanh(logits / cap) in place (Gemma-2 final logit soft-capping)
+void logit_softcap_(at::Tensor& logits, double cap) {
+  Args a("logit_softcap_", logits, "logits");
+  const Logits L = logits_rows(a, logits);
+  TORCH_CHECK(cap > 0, "logit_softcap_: cap > 0");
+  hipserve::launch_logit_softcap(L.p, L.bf16, L.stride, L.rows, L.V, (float)cap, cur_stream());
 }
 
 void logit_bias_apply(at::Tensor& logits, const at::Tensor& slot, const at::Tensor& ids, const at::Tensor& vals,
@@ -1344,8 +1357,8 @@ void vision_attention(at::Tensor& out, at::Tensor& qkv, const at::Tensor& cos_si
   X(fused_add_rmsnorm, "(Tensor(a!) out, Tensor x, Tensor(b!) residual, Tensor weight, float eps, Tensor(c!)? out8=None, Tensor(d!)? xs8=None) -> ()") \
   X(silu_and_mul, "(Tensor(a!) out, Tensor x) -> ()") \
   X(rope_cache, "(Tensor(a!) qkv, Tensor positions, Tensor slots, Tensor cos_sin, Tensor(b!) k_cache, Tensor(c!) v_cache, int nq, int nkv, int head_dim, int mode) -> ()") \
-  X(paged_decode, "(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor context_lens, Tensor(b!) tmp_out, Tensor(c!) tmp_ml, int nq, int nkv, int part_size, float scale, int window=0, Tensor(d!)? out16=None) -> ()") \
-  X(prefill_attention, "(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor cu_q, Tensor ctx_lens, Tensor tiles, int nq, int nkv, float scale, int window=0) -> ()") \
+  X(paged_decode, "(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor context_lens, Tensor(b!) tmp_out, Tensor(c!) tmp_ml, int nq, int nkv, int part_size, float scale, int window=0, Tensor(d!)? out16=None, float softcap=0.0) -> ()") \
+  X(prefill_attention, "(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor cu_q, Tensor ctx_lens, Tensor tiles, int nq, int nkv, float scale, int window=0, float softcap=0.0) -> ()") \
   X(qk_rmsnorm, "(Tensor(a!) qkv, Tensor q_w, Tensor k_w, int nq, int nkv, int head_dim, float eps) -> ()") \
   X(gelu_and_mul, "(Tensor(a!) out, Tensor x) -> ()") \
   X(gguf_gemm, "(Tensor(a!) out, Tensor x, Tensor q, Tensor d, Tensor m, int qtype, int row_bytes, int N, int K, Tensor(b!) ws, int splits) -> ()") \
@@ -1365,12 +1378,13 @@ void vision_attention(at::Tensor& out, at::Tensor& qkv, const at::Tensor& cos_si
   X(splitk_add_rmsnorm, "(Tensor(a!) out, Tensor(b!) residual, Tensor ws, int splits, Tensor weight, float eps, Tensor(c!)? out16=None, Tensor(d!)? out8=None, Tensor(e!)? xs8=None) -> ()") \
   X(splitk_post_add_rmsnorm, "(Tensor(a!) out, Tensor(b!) residual, Tensor ws, int splits, Tensor w_post, Tensor w_next, float eps, Tensor(c!)? out16=None, Tensor(d!)? out8=None, Tensor(e!)? xs8=None) -> ()") \
   X(splitk_glu, "(Tensor(a!) act, Tensor ws, int splits, bool gelu, Tensor(b!)? act16=None) -> ()") \
-  X(paged_decode_qkv, "(Tensor(a!) out, Tensor ws, int splits, Tensor positions, Tensor slots, Tensor cos_sin, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor block_tables, Tensor context_lens, Tensor(d!) tmp_out, Tensor(e!) tmp_ml, int nq, int nkv, int part_size, float scale, int window, int mode, Tensor(f!)? out16=None, Tensor? q_norm=None, Tensor? k_norm=None, float eps=1e-6) -> ()") \
+  X(paged_decode_qkv, "(Tensor(a!) out, Tensor ws, int splits, Tensor positions, Tensor slots, Tensor cos_sin, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor block_tables, Tensor context_lens, Tensor(d!) tmp_out, Tensor(e!) tmp_ml, int nq, int nkv, int part_size, float scale, int window, int mode, Tensor(f!)? out16=None, Tensor? q_norm=None, Tensor? k_norm=None, float eps=1e-6, float softcap=0.0) -> ()") \
   X(splitk_reduce, "(Tensor(a!) out, Tensor ws, int splits) -> ()") \
   X(splitk_rope_cache, "(Tensor(a!) qkv, Tensor ws, int splits, Tensor positions, Tensor slots, Tensor cos_sin, Tensor(b!) k_cache, Tensor(c!) v_cache, int nq, int nkv, int head_dim, int mode, Tensor? bias=None, Tensor? q_w=None, Tensor? k_w=None, float eps=1e-6) -> ()") \
   X(skinny_gemm, "(Tensor(a!) out, Tensor x, Tensor w, int rt, int kw) -> ()") \
   X(penalty_apply, "(Tensor(a!) logits, Tensor slot, Tensor pres, Tensor freq, Tensor rep, Tensor counts, Tensor seen) -> ()") \
   X(logit_bias_apply, "(Tensor(a!) logits, Tensor slot, Tensor ids, Tensor vals, Tensor n) -> ()") \
+  X(logit_softcap_, "(Tensor(a!) logits, float cap) -> ()") \
   X(penalty_update, "(Tensor tok, Tensor slot, Tensor(a!) counts, Tensor(b!) seen) -> ()") \
   X(penalty_init, "(Tensor(a!) counts, Tensor(b!) seen, Tensor slots, Tensor off, Tensor n_prompt, Tensor toks) -> ()") \
   X(top_logprobs, "(Tensor logits, Tensor nreq, Tensor(a!) out_ids, Tensor(b!) out_lp) -> ()") \

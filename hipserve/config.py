@@ -90,20 +90,22 @@ class ModelConfig:
     num_experts_per_tok: int = 0
     bos_token_id: int | None = 128000
     eos_token_id: tuple = (128001, 128009)
-    # ---- family options (Qwen2/Qwen3/Qwen3-MoE/Gemma-3/Phi-3; defaults = Llama/Mixtral)
-    family: str = "llama"                 # llama | mixtral | qwen2 | qwen3 | qwen3_moe | gemma3 | phi3
+    # ---- family options (Qwen2/Qwen3/Qwen3-MoE/Gemma-2/Gemma-3/Phi-3; defaults = Llama/Mixtral)
+    family: str = "llama"                 # llama | mixtral | qwen2 | qwen3 | qwen3_moe | gemma2 | gemma3 | phi3
     qkv_bias: bool = False                # Qwen2: q/k/v projections carry a bias
     qk_norm: bool = False                 # Qwen3 / Gemma-3: per-head RMSNorm of q and k before RoPE
     moe_intermediate_size: int = 0        # expert width when it differs from intermediate_size (Qwen3-MoE)
     norm_topk_prob: bool = True           # renormalise the top-k routing weights (Mixtral: always)
     hidden_act: str = "silu"              # silu | gelu_tanh (Gemma GeGLU)
-    sandwich_norm: bool = False           # Gemma-3: RMSNorm on the attention / MLP outputs too
+    sandwich_norm: bool = False           # Gemma-2 / -3: RMSNorm on the attention / MLP outputs too
     norm_offset: bool = False             # Gemma RMSNorm: x * (1 + w)
     embed_scale: float = 1.0              # Gemma: embeddings * sqrt(hidden)
     attn_scale: float = 0.0               # softmax scale (0 = 1/sqrt(head_dim)); Gemma: query_pre_attn_scalar^-0.5
     sliding_window: int = 0               # window of the sliding-attention layers (0 = none)
     layer_windows: tuple = ()             # per-layer window (0 = full attention); empty = all full
     rope_local_theta: float = 0.0         # RoPE base of the sliding layers (Gemma-3: 10000; 0 = rope_theta)
+    attn_softcap: float = 0.0             # Gemma-2: attention scores cap * tanh(s / cap) before the masks (0 = off)
+    final_softcap: float = 0.0            # Gemma-2: the same on the final logits (0 = off)
     partial_rotary_factor: float = 1.0
     # Qwen3-VL: interleaved multimodal RoPE (rotary pairs split T/H/W by this
     # section table; text tokens have t = h = w so it reduces to plain RoPE)
@@ -175,7 +177,7 @@ class ModelConfig:
             rope_theta=theta,
             rope_scaling=scaling,
             max_position_embeddings=d.get("max_position_embeddings", 4096),
-            tie_word_embeddings=d.get("tie_word_embeddings", family == "gemma3"),
+            tie_word_embeddings=d.get("tie_word_embeddings", family in ("gemma2", "gemma3")),
             bos_token_id=d.get("bos_token_id"),
             eos_token_id=eos,
             partial_rotary_factor=float(d.get("partial_rotary_factor", 1.0) or 1.0),
@@ -218,6 +220,17 @@ class ModelConfig:
                       sliding_window=win,
                       layer_windows=tuple(win if t == "sliding_attention" else 0 for t in types),
                       rope_local_theta=local_theta)
+        elif family == "gemma2":
+            # Gemma-3's block without the q/k norm and the local RoPE base, plus the two caps;
+            # Hub files carry no layer_types: even layers slide, odd layers are global
+            types = d.get("layer_types") or ["full_attention" if i % 2 else "sliding_attention" for i in range(L)]
+            win = int(d.get("sliding_window") or 0)
+            kw.update(hidden_act="gelu_tanh", sandwich_norm=True, norm_offset=True, embed_scale=float(H) ** 0.5,
+                      attn_scale=float(d.get("query_pre_attn_scalar") or D) ** -0.5,
+                      sliding_window=win,
+                      layer_windows=tuple(win if t == "sliding_attention" else 0 for t in types),
+                      attn_softcap=float(d.get("attn_logit_softcapping") or 0.0),
+                      final_softcap=float(d.get("final_logit_softcapping") or 0.0))
         return ModelConfig(**kw)
 
     def replace(self, **kw) -> "ModelConfig":
@@ -234,6 +247,8 @@ def _family_of(arch: str, mtype: str, d: dict) -> str:
         return "qwen2"
     if t.startswith("gemma3") or a.startswith("gemma3"):
         return "gemma3"
+    if t == "gemma2" or a.startswith("gemma2"):
+        return "gemma2"
     if t == "phi3" or a.startswith("phi3"):
         return "phi3"
     if t == "mixtral" or "mixtral" in a or d.get("num_local_experts"):
@@ -285,6 +300,18 @@ def _gemma3(name: str, *, hidden_size: int, num_layers: int, sliding_window: int
                        embed_scale=hidden_size ** 0.5, attn_scale=256 ** -0.5, sliding_window=sliding_window,
                        layer_windows=tuple(sliding_window if (i + 1) % 6 else 0 for i in range(num_layers)),
                        rope_local_theta=1e4, bos_token_id=2, eos_token_id=(1, 106), **kw)
+
+
+def _gemma2(name: str, *, hidden_size: int, num_layers: int, head_dim: int = 256,
+            query_pre_attn_scalar: int | None = None, **kw) -> ModelConfig:
+    """Gemma-2 2B / 9B / 27B: sliding (4096) and global layers alternate from a sliding layer 0,
+    one RoPE base, no q/k norm, attention scores capped at 50 and final logits at 30."""
+    return ModelConfig(name=name, family="gemma2", hidden_size=hidden_size, num_layers=num_layers, head_dim=head_dim,
+                       vocab_size=256000, rms_norm_eps=1e-6, rope_theta=1e4, max_position_embeddings=8192,
+                       tie_word_embeddings=True, hidden_act="gelu_tanh", sandwich_norm=True, norm_offset=True,
+                       embed_scale=hidden_size ** 0.5, attn_scale=(query_pre_attn_scalar or head_dim) ** -0.5,
+                       sliding_window=4096, layer_windows=tuple(0 if i % 2 else 4096 for i in range(num_layers)),
+                       attn_softcap=50.0, final_softcap=30.0, bos_token_id=2, eos_token_id=(1, 107), **kw)
 
 
 # Public architecture hyper-parameters (SURVEY §2.E). Random-init weights of these
@@ -348,6 +375,13 @@ PRESETS: dict[str, ModelConfig] = {
                           intermediate_size=10240),
     "gemma-3-12b": _gemma3("gemma-3-12b", hidden_size=3840, num_layers=48, num_heads=16, num_kv_heads=8,
                            intermediate_size=15360),
+    # Gemma-2: published config.json values (27B: head_dim 128, query_pre_attn_scalar = hidden / heads)
+    "gemma-2-2b": _gemma2("gemma-2-2b", hidden_size=2304, num_layers=26, num_heads=8, num_kv_heads=4,
+                          intermediate_size=9216),
+    "gemma-2-9b": _gemma2("gemma-2-9b", hidden_size=3584, num_layers=42, num_heads=16, num_kv_heads=8,
+                          intermediate_size=14336),
+    "gemma-2-27b": _gemma2("gemma-2-27b", hidden_size=4608, num_layers=46, num_heads=32, num_kv_heads=16,
+                           head_dim=128, intermediate_size=36864, query_pre_attn_scalar=144),
     "phi-3-mini": ModelConfig(name="phi-3-mini", family="phi3", hidden_size=3072, num_layers=32,
                               num_heads=32, num_kv_heads=32, head_dim=96, intermediate_size=8192,
                               vocab_size=32064, rope_theta=10000.0, max_position_embeddings=4096,

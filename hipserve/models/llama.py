@@ -757,10 +757,10 @@ class LlamaModel(MoEMixin):
                            kc, vc, nq, nkv, D, cfg.rope_mode)
             if Tp:
                 ops.prefill_attention(attn[:Tp], qkv[:Tp], kc, vc, meta.bt_prefill, meta.cu_q,
-                                      meta.ctx_prefill, meta.tiles, nq, nkv, self.scale, win)
+                                      meta.ctx_prefill, meta.tiles, nq, nkv, self.scale, win, cfg.attn_softcap)
             if Td:  # rows past Tp + Td: prefill padding (model_runner._pad_rows)
                 ops.paged_decode(attn[Tp:Tp + Td], qkv[Tp:Tp + Td], kc, vc, meta.bt_decode, meta.ctx_decode,
-                                 tmp_out, tmp_ml, nq, nkv, part, self.scale, win)
+                                 tmp_out, tmp_ml, nq, nkv, part, self.scale, win, None, cfg.attn_softcap)
             x8 = self._x8p(xn, lw.wgu, glu=True)
             self._rowpar_norm(xn, residual, attn, lw.wo, lw.post_attn_norm, lw.ln2, x8)
             nxt = self.layers[i + 1].ln1 if i + 1 < L else self.norm
@@ -849,7 +849,7 @@ class LlamaModel(MoEMixin):
                 # RoPE + KV write + attention in one kernel, straight from the partials
                 op.paged_decode_qkv(attn, pt[0], pt[1], meta.positions, meta.slot_mapping, self.cos_sin, kc, vc,
                                     meta.bt_decode, meta.ctx_decode, tmp_out, tmp_ml, nq, nkv, part, self.scale,
-                                    0, cfg.rope_mode, attn16, lw.q_norm, lw.k_norm, eps)
+                                    0, cfg.rope_mode, attn16, lw.q_norm, lw.k_norm, eps, cfg.attn_softcap)
             elif pt is not None:  # + q/k/v bias and per-head q/k RMSNorm of the family, if any
                 ws, S = pt
                 qkv = torch.empty(T, lw.wqkv.shape[0], device=h.device, dtype=h.dtype)
@@ -865,7 +865,7 @@ class LlamaModel(MoEMixin):
                                cfg.rope_mode)
             if pt is None or not fuse_qa:
                 ops.paged_decode(attn, qkv, kc, vc, meta.bt_decode, meta.ctx_decode, tmp_out, tmp_ml,
-                                 nq, nkv, part, self.scale, win, attn16)
+                                 nq, nkv, part, self.scale, win, attn16, cfg.attn_softcap)
             xn16, xn8 = self._decode_rowpar_norm(xn, residual, attn, lw.wo, attn16, lw.post_attn_norm, lw.ln2, lw.wgu)
             nxt = self.layers[i + 1].ln1 if i + 1 < L else self.norm
             if lw.router is not None:  # MoE MLP: routed expert GEMMs, then residual + next norm
@@ -1002,8 +1002,10 @@ class LlamaModel(MoEMixin):
 
     def compute_logits(self, hidden: torch.Tensor) -> torch.Tensor:
         logits = self.linear(hidden, self.lm_head)
-        logits = self.tp.all_gather_lastdim(logits)
-        return logits[:, : self.cfg.vocab_size]
+        logits = self.tp.all_gather_lastdim(logits)[:, : self.cfg.vocab_size]
+        if self.cfg.final_softcap > 0:  # Gemma-2: everything downstream sees the capped logits
+            self.ops.logit_softcap_(logits, self.cfg.final_softcap)
+        return logits
 
     # ---------------------------------------------------------------- kv cache
     def kv_bytes_per_block(self, block_size: int) -> int:

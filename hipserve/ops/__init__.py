@@ -88,15 +88,15 @@ class KernelOps:
         self._op.rope_cache(qkv, positions, slots, cos_sin, k_cache, v_cache, nq, nkv, D, mode)
 
     def paged_decode(self, out, q, k_cache, v_cache, block_tables, context_lens, tmp_out, tmp_ml,
-                     nq, nkv, part_size, scale, window=0, out16=None):
+                     nq, nkv, part_size, scale, window=0, out16=None, softcap=0.0):
         self._op.paged_decode(out, q, k_cache, v_cache, block_tables, context_lens, tmp_out, tmp_ml,
-                              nq, nkv, part_size, scale, window, out16)
+                              nq, nkv, part_size, scale, window, out16, softcap)
         return out
 
     def prefill_attention(self, out, q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tiles,
-                          nq, nkv, scale, window=0):
+                          nq, nkv, scale, window=0, softcap=0.0):
         self._op.prefill_attention(out, q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tiles,
-                                   nq, nkv, scale, window)
+                                   nq, nkv, scale, window, softcap)
         return out
 
     def sample(self, out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds=True,
@@ -111,6 +111,11 @@ class KernelOps:
 
     def logit_bias_apply(self, logits, slot, ids, vals, n):
         self._op.logit_bias_apply(logits, slot, ids, vals, n)
+
+    def logit_softcap_(self, logits, cap):
+        """logits = cap * tanh(logits / cap) in place (Gemma-2 final logit soft-capping)."""
+        self._op.logit_softcap_(logits, cap)
+        return logits
 
     def penalty_update(self, tok, slot, counts, seen):
         self._op.penalty_update(tok, slot, counts, seen)
@@ -183,19 +188,19 @@ class ReferenceOps:
         ref.rope_cache(qkv, positions, slots, cos_sin, k_cache, v_cache, nq, nkv, D, mode)
 
     def paged_decode(self, out, q, k_cache, v_cache, block_tables, context_lens, tmp_out, tmp_ml,
-                     nq, nkv, part_size, scale, window=0, out16=None):
+                     nq, nkv, part_size, scale, window=0, out16=None, softcap=0.0):
         B = context_lens.shape[0]
         D = k_cache.shape[3]
         out[:B, : nq * D].copy_(ref.paged_decode(q, k_cache, v_cache, block_tables, context_lens,
-                                                 nq, nkv, scale, window).view(B, nq * D))
+                                                 nq, nkv, scale, window, softcap).view(B, nq * D))
         return out
 
     def prefill_attention(self, out, q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tiles,
-                          nq, nkv, scale, window=0):
+                          nq, nkv, scale, window=0, softcap=0.0):
         D = k_cache.shape[3]
         T = int(cu_q[-1])
         out[:T, : nq * D].copy_(ref.prefill_attention(q, k_cache, v_cache, block_tables, cu_q,
-                                                      ctx_lens, nq, nkv, scale, window).view(T, nq * D))
+                                                      ctx_lens, nq, nkv, scale, window, softcap).view(T, nq * D))
         return out
 
     def penalty_apply(self, logits, slot, pres, freq, rep, counts, seen):
@@ -203,6 +208,9 @@ class ReferenceOps:
 
     def logit_bias_apply(self, logits, slot, ids, vals, n):
         ref.logit_bias_apply(logits, slot, ids, vals, n)
+
+    def logit_softcap_(self, logits, cap):
+        return ref.logit_softcap(logits, cap)
 
     def penalty_update(self, tok, slot, counts, seen):
         ref.penalty_update(tok, slot, counts, seen)

@@ -171,9 +171,21 @@ def _gather_kv(k_cache, v_cache, block_table, n):
     return k, v
 
 
-def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nq, nkv, scale, window=0):
+def softcap_scores(s, softcap):
+    """Gemma-2 logit soft-capping of fp32 scores, ``softcap * tanh(s / softcap)``; 0 = off.
+    Applied to the scaled scores before any mask."""
+    return torch.tanh(s / softcap) * softcap if softcap > 0 else s
+
+
+def logit_softcap(logits, cap):
+    """``cap * tanh(logits / cap)`` in place (fp32 math, one rounding to the logits' dtype)."""
+    logits.copy_(torch.tanh(logits.float() / cap) * cap)
+    return logits
+
+
+def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nq, nkv, scale, window=0, softcap=0.0):
     """q [B, nq*D (+extra)] -> out [B, nq, D] (fp32 math). window > 0: only the
-    last ``window`` keys (sliding-window layers)."""
+    last ``window`` keys (sliding-window layers). softcap > 0: capped scores."""
     D = k_cache.shape[3]
     B = context_lens.shape[0]
     G = nq // nkv
@@ -186,15 +198,16 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nq, nkv, scale
         qb = q[b, : nq * D].view(nq, D).float()
         kf = k.float().repeat_interleave(G, dim=1)  # [n, nq, D]
         vf = v.float().repeat_interleave(G, dim=1)
-        s = torch.einsum("hd,nhd->hn", qb, kf) * scale
+        s = softcap_scores(torch.einsum("hd,nhd->hn", qb, kf) * scale, softcap)
         p = torch.softmax(s, dim=-1)
         out[b] = torch.einsum("hn,nhd->hd", p, vf).to(q.dtype)
     return out
 
 
-def prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nq, nkv, scale, window=0):
+def prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nq, nkv, scale, window=0, softcap=0.0):
     """q [T, nq*D (+extra)] -> out [T, nq, D]; causal over absolute positions;
-    window > 0: keys within ``window - 1`` positions before the query."""
+    window > 0: keys within ``window - 1`` positions before the query.
+    softcap > 0: capped scores, capped before the masks."""
     D = k_cache.shape[3]
     G = nq // nkv
     T = int(cu_q[-1])
@@ -208,7 +221,7 @@ def prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nq, nkv
         qs = q[q0:q1, : nq * D].view(ql, nq, D).float()
         kf = k.float().repeat_interleave(G, dim=1)
         vf = v.float().repeat_interleave(G, dim=1)
-        s = torch.einsum("qhd,nhd->hqn", qs, kf) * scale
+        s = softcap_scores(torch.einsum("qhd,nhd->hqn", qs, kf) * scale, softcap)
         qpos = torch.arange(ctx - ql, ctx, device=q.device)[:, None]
         kpos = torch.arange(ctx, device=q.device)[None, :]
         mask = kpos > qpos

@@ -100,8 +100,13 @@ def bench_sample(ops):
     emit(op="logit_bias_apply", V=V, B=B, entries=E, us=round(us, 1), graph=timer is graph_time)
 
 
+def softcaps():
+    """BENCH_SOFTCAP="0,50": the attention benches time every shape once per value, in the same
+    run on the same tensors (0 = the uncapped kernel, > 0 = Gemma-2 score soft-capping)."""
+    return [float(x) for x in os.environ.get("BENCH_SOFTCAP", "0").split(",")]
+
+
 def bench_decode(ops):
-    import os
     D = int(os.environ.get("BENCH_D", "128"))  # head_dim: 64 / 96 / 128 / 256
     parts = [int(x) for x in os.environ.get("DECODE_PARTS", "512").split(",")]
     bss = [int(x) for x in os.environ.get("DECODE_BS", "16").split(",")]  # KV block sizes
@@ -128,15 +133,16 @@ def bench_decode(ops):
         tm = torch.empty(B, nq, mp, 2, device=DEV)
         out = torch.empty(B, nq * D, device=DEV, dtype=torch.bfloat16)
         it = [0]
+        for cap in softcaps():
+            def call():
+                i = it[0] % ncopy
+                it[0] += 1
+                ops.paged_decode(out, q, kcs[i], vcs[i], bt, cl, to, tm, nq, nkv, part, 1 / math.sqrt(D), 0, None, cap)
 
-        def call():
-            i = it[0] % ncopy
-            it[0] += 1
-            ops.paged_decode(out, q, kcs[i], vcs[i], bt, cl, to, tm, nq, nkv, part, 1 / math.sqrt(D))
-
-        us = timeit(call)
-        emit(op="paged_decode", D=D, kv="fp8" if f8 else "bf16", B=B, ctx=ctx, nq=nq, nkv=nkv, part=part, bs=bs, cold=ncopy > 1,
-             nt=os.environ.get("HIPSERVE_DECODE_NT", "1"), us=round(us, 1), TBps=round(byts / us / 1e6, 2))
+            us = timeit(call)
+            emit(op="paged_decode", D=D, kv="fp8" if f8 else "bf16", B=B, ctx=ctx, nq=nq, nkv=nkv, part=part, bs=bs,
+                 cold=ncopy > 1, nt=os.environ.get("HIPSERVE_DECODE_NT", "1"), softcap=cap, us=round(us, 1),
+                 TBps=round(byts / us / 1e6, 2))
         del kcs, vcs
 
 
@@ -164,10 +170,11 @@ def bench_prefill(ops):
         for ver in vers:  # v1: per-wave L2 K/V reads (HIPSERVE_PREFILL_ATTN_V1=1)
             os.environ["HIPSERVE_PREFILL_ATTN_V1"] = "1" if ver == "v1" else "0"
             os.environ["HIPSERVE_PREFILL_ATTN_WAVES"] = "8" if ver == "v2w8" else "4"
-            us = timeit(lambda: ops.prefill_attention(out, q, kc, vc, bt, cu, ctx, tiles, nq, nkv,
-                                                      1 / math.sqrt(D)), n=10)
-            emit(op="prefill_attention", D=D, ver=ver, S=S, nseq=nseq, nq=nq, nkv=nkv, us=round(us, 1),
-                 TFLOPs=round(flops / us / 1e6, 1))
+            for cap in softcaps():
+                us = timeit(lambda: ops.prefill_attention(out, q, kc, vc, bt, cu, ctx, tiles, nq, nkv,
+                                                          1 / math.sqrt(D), 0, cap), n=10)
+                emit(op="prefill_attention", D=D, ver=ver, kv="fp8" if kvt == torch.float8_e4m3fn else "bf16", S=S,
+                     nseq=nseq, nq=nq, nkv=nkv, softcap=cap, us=round(us, 1), TFLOPs=round(flops / us / 1e6, 1))
         os.environ.pop("HIPSERVE_PREFILL_ATTN_V1", None)
 
 
