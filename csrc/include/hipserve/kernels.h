@@ -60,7 +60,7 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
                               int bt_stride, const int* cu_q, const int* ctx_lens,
                               const int* tiles, int ntiles, int nq, int nkv, int D,
                               int block_size, float scale, int window, hipStream_t s, bool kv_f8 = false,
-                              float softcap = 0.f);
+                              float softcap = 0.f, const int* limits = nullptr);
 
 // sampling.hip
 // ws: fp32 workspace of sample_workspace_floats(rows, V) for the multi-CU path
@@ -320,7 +320,11 @@ void launch_layernorm(void* out, void* residual, const void* x, const void* w, c
 void launch_gelu(void* x, long n, bool tanh_approx, hipStream_t s);
 // qkv [T, 3 nh D]: 2D RoPE of q, k in place (fp32 table [T, D]), then bidirectional attention
 // within each segment [cu[i], cu[i+1]) -> out [T, nh D]; tiles [ntiles, 2] = (segment, first row)
-// in steps of 128 rows.
+// in steps of 128 rows. cos_sin == nullptr: no RoPE (SigLIP), the rotation kernel is not launched.
 void launch_vision_attention(void* out, void* qkv, const float* cos_sin, const int* cu, const int* tiles,
                              int ntiles, int T, int nh, int D, float scale, hipStream_t s);
+// Gemma-3 projector front: x [images * g * g, C] in patch order -> out [images * (g/k)^2, C]:
+// k x k average pool, then RMSNorm with (1 + w) (fp32, one rounding to bf16)
+void launch_vision_pool_rmsnorm(void* out, const void* x, const void* w, int images, int g, int k, int C, float eps,
+                                hipStream_t s);
 }  // namespace hipserve

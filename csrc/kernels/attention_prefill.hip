@@ -43,7 +43,14 @@ typedef unsigned short u16x4v __attribute__((ext_vector_type(4)));
 // kCap (both kernels): logit soft-capping (Gemma-2), score = softcap * tanh(q.k * scale /
 // softcap) on the raw score BEFORE the causal / window masks (a capped -inf would be a live
 // score of -softcap); its own instantiations, so the uncapped kernels are the code they were
-template <int D, typename KV, bool kCap = false>
+// kLim (both kernels): per-row key limits (Gemma-3 image blocks attend in both directions):
+// key kk is visible to the row at pos iff kk <= max(pos, limits[row]) and the window's lower
+// bound (on pos) holds; limits is indexed like q's rows, holds absolute key positions and is
+// non-decreasing within a sequence, so a wave's last key tile comes from its last row's
+// limit. Its own instantiations again; limits are clamped to the context (no key past it)
+// (kLim = false leaves `limits` unread: those instantiations compile to the registers, LDS and
+// scratch they had, profiles/gemma3_mm_attn_resources.md)
+template <int D, typename KV, bool kCap = false, bool kLim = false>
 __global__ __launch_bounds__(256) void prefill_attn_kernel(
     unsigned short* __restrict__ out, long out_stride,
     const unsigned short* __restrict__ q, long q_stride,
@@ -52,7 +59,7 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(
     const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
     const int* __restrict__ tiles, int nq, int nkv, int block_size,
-    float scale, int window, float softcap = 0.f) {
+    float scale, int window, float softcap, const int* __restrict__ limits) {
   constexpr int KS = D / 16;   // k-steps of QK (K = 16 per MFMA)
   constexpr int NB = D / 32;   // 32-row d blocks of O^T
   const int seq = tiles[2 * blockIdx.x], r0 = tiles[2 * blockIdx.x + 1];
@@ -67,7 +74,12 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(
   if (wrow0 >= qlen) return;
   const int row = min(wrow0 + qi, qlen - 1);
   const int pos = ctx - qlen + row;        // absolute position of this query row
-  const int max_key = ctx - qlen + min(wrow0 + 31, qlen - 1);
+  int max_key = ctx - qlen + min(wrow0 + 31, qlen - 1);
+  int lim = pos;                           // last key this row sees
+  if constexpr (kLim) {
+    lim = min(max(pos, limits[q0 + row]), ctx - 1);
+    max_key = min(max(max_key, limits[q0 + min(wrow0 + 31, qlen - 1)]), ctx - 1);
+  }
   const int* btab = block_tables + (long)seq * bt_stride;
   const long head_stride = (long)block_size * D;
 
@@ -132,7 +144,7 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(
       float sv;  // the log2-domain score
       if constexpr (kCap) sv = softcap_apply(st[r], cap);
       else sv = st[r] * sl2;
-      const float v = (kk <= pos && (window <= 0 || kk > pos - window)) ? sv : -INFINITY;
+      const float v = (kk <= lim && (window <= 0 || kk > pos - window)) ? sv : -INFINITY;
       st[r] = v;
       mx = fmaxf(mx, v);
     }
@@ -211,13 +223,13 @@ constexpr int PA2_KT = 64, PA2_KLD = 128 + 8, PA2_VLD = 64 + 8;
 // 256 of two waves per SIMD and spilled: 1.4-1.5x slower, profiles/r5_prefill_attn_bench.log.)
 // KV: cache element, bf16 or e4m3; e4m3 pieces (8 bytes) are widened to bf16 on their way
 // into the LDS ring, so the MFMA / softmax body is the same for both
-template <int HG, int NWV, typename KV, bool kCap = false>
+template <int HG, int NWV, typename KV, bool kCap = false, bool kLim = false>
 __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
     unsigned short* __restrict__ out, long out_stride, const unsigned short* __restrict__ q, long q_stride,
     const KV* __restrict__ k_cache, const KV* __restrict__ v_cache,
     const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ cu_q,
     const int* __restrict__ ctx_lens, const int* __restrict__ tiles, int nq, int nkv, int block_size,
-    float scale, int window, int prio, float softcap = 0.f) {
+    float scale, int window, int prio, float softcap, const int* __restrict__ limits) {
   constexpr int D = 128, KS = 8, NB = 4;
   constexpr int RB = NWV / HG, QR = 32 * RB, SUB = 128 / QR;
   constexpr int NT = 64 * NWV, NP = 1024 / NT;  // threads; K (and V^T) 16-byte pieces per thread
@@ -247,7 +259,15 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
   const int pos = ctx - qlen + row;
   const int wmax_key = ctx - qlen + min(wrow0 + 31, qlen - 1);
   const int wmin_pos = ctx - qlen + wrow0;
-  const int nkt = (ctx - qlen + min(r0 + QR - 1, qlen - 1)) / PA2_KT + 1;
+  int nkt = (ctx - qlen + min(r0 + QR - 1, qlen - 1)) / PA2_KT + 1;
+  // limits (kLim): this row's last key and the wave's (its last row's); the tile count, the
+  // staged block ids and the stage_load lookahead follow the workgroup's (its last row's)
+  [[maybe_unused]] int lim_pos = pos, wlim_key = wmax_key;
+  if constexpr (kLim) {
+    lim_pos = min(max(pos, limits[q0 + row]), ctx - 1);
+    wlim_key = min(max(wmax_key, limits[q0 + min(wrow0 + 31, qlen - 1)]), ctx - 1);
+    nkt = min(max(nkt * PA2_KT - 1, limits[q0 + min(r0 + QR - 1, qlen - 1)]), ctx - 1) / PA2_KT + 1;
+  }
   // sliding window: rows see keys [pos - window + 1, pos]; the workgroup starts at
   // the tile holding its first row's lowest key
   const int kt0 = window > 0 ? max(0, ctx - qlen + r0 - window + 1) / PA2_KT : 0;
@@ -320,7 +340,7 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
 
   auto compute = [&](int kt, int buf) __attribute__((always_inline)) {
     const int kbase = kt * PA2_KT;
-    if (wactive && kbase <= wmax_key && (window <= 0 || kbase + PA2_KT - 1 > wmin_pos - window)) {
+    if (wactive && kbase <= (kLim ? wlim_key : wmax_key) && (window <= 0 || kbase + PA2_KT - 1 > wmin_pos - window)) {
       const unsigned short* kb = &kl[buf][qi * PA2_KLD + 8 * half];
       f32x16 st[2];
 #pragma unroll
@@ -359,8 +379,9 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
       // diagonal tile (causal mask) or a tile crossing some row's window start
       // (key offsets inside the tile are compile-time per accumulator slot: one compare +
       // select per score against the lane's limit, the window test only when one is set)
+      // (kLim: the tiles from the wave's lowest pos up to its highest limit take the first test)
       if (kbase + PA2_KT - 1 > wmin_pos || (window > 0 && kbase <= wmax_key - window)) {
-        const int lim = pos - kbase - 8 * half;  // slot offset > lim: a future key
+        const int lim = (kLim ? lim_pos : pos) - kbase - 8 * half;  // slot offset > lim: a hidden (future) key
         if (window <= 0) {
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2)
@@ -368,7 +389,8 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
             for (int r = 0; r < 16; ++r)
               if (32 * h2 + 16 * (r >> 3) + 4 * ((r >> 2) & 1) + (r & 3) > lim) st[h2][r] = -INFINITY;
         } else {
-          const int wlo = lim - window;  // slot offset <= wlo: before the window
+          // slot offset <= wlo: before the window (which hangs on pos, not on the limit)
+          const int wlo = kLim ? pos - kbase - 8 * half - window : lim - window;
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
@@ -470,7 +492,8 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
                               const void* v_cache, const int* block_tables,
                               int bt_stride, const int* cu_q, const int* ctx_lens,
                               const int* tiles, int ntiles, int nq, int nkv, int D,
-                              int block_size, float scale, int window, hipStream_t s, bool kv_f8, float softcap) {
+                              int block_size, float scale, int window, hipStream_t s, bool kv_f8, float softcap,
+                              const int* limits) {
   if (ntiles <= 0) return;
   const int G = nq / nkv;
   // v2 keeps the sequence's block ids in LDS next to its 70 KiB K / V ring (160 KiB per CU)
@@ -505,7 +528,18 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
     (void)attr;                                                                                             \
     prefill_attn_v2_kernel<hg, nw, KVT, CAP><<<g2, 64 * nw, bt_lds, s>>>(                                   \
         o2, out_stride, q2, q_stride, KP, VP, block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,      \
-        block_size, scale, window, prio, softcap);                                                          \
+        block_size, scale, window, prio, softcap, nullptr);                                                          \
+  } while (0)
+#define PA2_LAUNCH_LIM(hg, nw, KVT, KP, VP)                                                                 \
+  do {                                                                                                      \
+    static bool attr = [] {                                                                                 \
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_attn_v2_kernel<hg, nw, KVT, false, true>),   \
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;      \
+    }();                                                                                                    \
+    (void)attr;                                                                                             \
+    prefill_attn_v2_kernel<hg, nw, KVT, false, true><<<g2, 64 * nw, bt_lds, s>>>(                                    \
+        o2, out_stride, q2, q_stride, KP, VP, block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,      \
+        block_size, scale, window, prio, 0.f, limits);                                                           \
   } while (0)
 #define PA2_LAUNCH_CAP(hg, nw, CAP)                                                                         \
   do {                                                                                                      \
@@ -514,7 +548,10 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
   } while (0)
 #define PA2_LAUNCH(hg, nw)                                                                                  \
   do {                                                                                                      \
-    if (softcap > 0.f) PA2_LAUNCH_CAP(hg, nw, true);                                                        \
+    if (limits != nullptr) { /* per-row key limits: no soft-capping (the binding refuses it) */             \
+      if (kv_f8) PA2_LAUNCH_LIM(hg, nw, unsigned char, k28, v28);                                          \
+      else PA2_LAUNCH_LIM(hg, nw, unsigned short, k2, v2);                                                  \
+    } else if (softcap > 0.f) PA2_LAUNCH_CAP(hg, nw, true);                                                 \
     else PA2_LAUNCH_CAP(hg, nw, false);                                                                     \
   } while (0)
     if (nwv == 8) {
@@ -527,6 +564,7 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
     }
 #undef PA2_LAUNCH
 #undef PA2_LAUNCH_CAP
+#undef PA2_LAUNCH_LIM
 #undef PA2_LAUNCH_KV
     return;
   }
@@ -541,17 +579,35 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
       prefill_attn_kernel<dd, unsigned char, CAP><<<grid, block, 0, s>>>(                                       \
           o, out_stride, qq, q_stride, static_cast<const unsigned char*>(k_cache),                              \
           static_cast<const unsigned char*>(v_cache), block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,  \
-          block_size, scale, window, softcap);                                                                  \
+          block_size, scale, window, softcap, nullptr);                                                                  \
     else                                                                                                        \
       prefill_attn_kernel<dd, unsigned short, CAP><<<grid, block, 0, s>>>(                                      \
           o, out_stride, qq, q_stride, kc, vc, block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,         \
-          block_size, scale, window, softcap);                                                                  \
+          block_size, scale, window, softcap, nullptr);                                                                  \
+  } while (0)
+#define PA1_LAUNCH_LIM(dd)                                                                                      \
+  do {                                                                                                          \
+    if (kv_f8)                                                                                                  \
+      prefill_attn_kernel<dd, unsigned char, false, true><<<grid, block, 0, s>>>(                                        \
+          o, out_stride, qq, q_stride, static_cast<const unsigned char*>(k_cache),                              \
+          static_cast<const unsigned char*>(v_cache), block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,  \
+          block_size, scale, window, 0.f, limits);                                                                   \
+    else                                                                                                        \
+      prefill_attn_kernel<dd, unsigned short, false, true><<<grid, block, 0, s>>>(                                       \
+          o, out_stride, qq, q_stride, kc, vc, block_tables, bt_stride, cu_q, ctx_lens, tiles, nq, nkv,         \
+          block_size, scale, window, 0.f, limits);                                                                   \
   } while (0)
 #define PA1_LAUNCH(dd)                                                                                          \
   do {                                                                                                          \
     if (softcap > 0.f) PA1_LAUNCH_CAP(dd, true);                                                                \
     else PA1_LAUNCH_CAP(dd, false);                                                                             \
   } while (0)
+  // per-row key limits (Gemma-3 image blocks): D = 128 / 256, no soft-capping (the binding refuses the rest)
+  if (limits != nullptr) {
+    if (D == 256) PA1_LAUNCH_LIM(256);
+    else PA1_LAUNCH_LIM(128);
+    return;
+  }
   // head_dim 256 (Gemma-3 1B / 4B / 12B) runs v1: 256 VGPRs + the accumulators in AGPRs at one
   // wave per SIMD, no scratch; a v2-class kernel there is a design of its own (README Limits)
   if (D == 256) PA1_LAUNCH(256);
@@ -559,6 +615,7 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
   else if (D == 96) PA1_LAUNCH(96);
   else PA1_LAUNCH(64);
 #undef PA1_LAUNCH
+#undef PA1_LAUNCH_LIM
 #undef PA1_LAUNCH_CAP
 }
 

@@ -118,6 +118,84 @@ void launch_layernorm(void* out, void* residual, const void* x, const void* w, c
 #undef LN_LAUNCH
 }
 
+// ---------------------------------------------------------------- pool + RMSNorm (Gemma-3 projector)
+// x [images * g * g, C] in patch order -> out [images * (g/k)^2, C]: the k x k average pool of
+// each image's g x g patch grid, then Gemma's RMSNorm ((1 + w), fp32 math, one rounding to
+// bf16). One wave per output row: a lane sums its 16-byte slices of the k * k source rows in
+// registers, the row's sum of squares is one DPP wave reduction (as in the row-norm kernels).
+template <int VPT>
+__global__ __launch_bounds__(256) void vision_pool_rmsnorm_kernel(unsigned short* __restrict__ out,
+                                                                  const unsigned short* __restrict__ x,
+                                                                  const unsigned short* __restrict__ w, int rows,
+                                                                  int g, int k, int C, float eps) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const int nvec = C >> 3;
+  const int go = g / k;                       // pooled side
+  const int img = row / (go * go), cell = row - img * go * go;
+  const int pr = cell / go, pc = cell - pr * go;
+  const unsigned short* src = x + ((long)img * g * g + (long)pr * k * g + (long)pc * k) * C;
+  float v[VPT][8];
+#pragma unroll
+  for (int i = 0; i < VPT; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
+  for (int a = 0; a < k; ++a)
+    for (int b = 0; b < k; ++b) {
+      const u16x8* xr = reinterpret_cast<const u16x8*>(src + ((long)a * g + b) * C);
+#pragma unroll
+      for (int i = 0; i < VPT; ++i) {
+        const int idx = lane + 64 * i;
+        if (idx < nvec) {
+          const u16x8 t = xr[idx];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[i][j] += bf16_to_f32(t[j]);
+        }
+      }
+    }
+  const float ik = 1.f / (float)(k * k);
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPT; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      v[i][j] *= ik;
+      q = fmaf(v[i][j], v[i][j], q);  // lanes past nvec hold zeros
+    }
+  const float inv = rsqrtf(wave_sum(q) / C + eps);
+  u16x8* orow = reinterpret_cast<u16x8*>(out + (long)row * C);
+#pragma unroll
+  for (int i = 0; i < VPT; ++i) {
+    const int idx = lane + 64 * i;
+    if (idx < nvec) {
+      const u16x8 wv = reinterpret_cast<const u16x8*>(w)[idx];
+      u16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = f32_to_bf16(v[i][j] * inv * (1.f + bf16_to_f32(wv[j])));
+      orow[idx] = o;
+    }
+  }
+}
+
+void launch_vision_pool_rmsnorm(void* out, const void* x, const void* w, int images, int g, int k, int C, float eps,
+                                hipStream_t s) {
+  const int rows = images * (g / k) * (g / k);
+  if (rows <= 0) return;
+  auto* o = static_cast<unsigned short*>(out);
+  auto* xx = static_cast<const unsigned short*>(x);
+  auto* ww = static_cast<const unsigned short*>(w);
+  const int nvec = C / 8;
+  dim3 grid(cdiv(rows, 4));
+#define VP_LAUNCH(vpt) vision_pool_rmsnorm_kernel<vpt><<<grid, 256, 0, s>>>(o, xx, ww, rows, g, k, C, eps)
+  if (nvec <= 64) VP_LAUNCH(1);
+  else if (nvec <= 128) VP_LAUNCH(2);
+  else if (nvec <= 192) VP_LAUNCH(3);
+  else if (nvec <= 256) VP_LAUNCH(4);
+  else VP_LAUNCH(8);
+#undef VP_LAUNCH
+}
+
 // ---------------------------------------------------------------- GELU (in place)
 template <bool kTanh>
 __global__ __launch_bounds__(256) void gelu_kernel(unsigned short* __restrict__ x, long nvec) {
@@ -389,7 +467,7 @@ void launch_vision_attention(void* out, void* qkv, const float* cos_sin, const i
   if (T <= 0 || ntiles <= 0) return;
   auto* q = static_cast<unsigned short*>(qkv);
   const unsigned rg = (unsigned)((2L * T * nh + 255) / 256);
-  switch (D) {
+  if (cos_sin != nullptr) switch (D) {  // no table: no RoPE (SigLIP's learned positions)
     case 64: vision_rope_kernel<64><<<rg, 256, 0, s>>>(q, cos_sin, T, nh); break;
     case 72: vision_rope_kernel<72><<<rg, 256, 0, s>>>(q, cos_sin, T, nh); break;
     case 80: vision_rope_kernel<80><<<rg, 256, 0, s>>>(q, cos_sin, T, nh); break;

@@ -519,7 +519,7 @@ void prefill_attention(at::Tensor& out, const at::Tensor& q, const at::Tensor& k
                        const at::Tensor& v_cache, const at::Tensor& block_tables,
                        const at::Tensor& cu_q, const at::Tensor& ctx_lens,
                        const at::Tensor& tiles, int64_t nq, int64_t nkv, double scale, int64_t window,
-                       double softcap) {
+                       double softcap, const c10::optional<at::Tensor>& limits) {
   Args a("prefill_attention", q, "q");
   const KvCache kv = kv_cache(a, k_cache, v_cache, nkv);
   const int D = kv.D;
@@ -533,9 +533,16 @@ void prefill_attention(at::Tensor& out, const at::Tensor& q, const at::Tensor& k
   const int* cu = a.as<int>(cu_q, "cu_q", ROWS);
   const int* cl = a.as<int>(ctx_lens, "ctx_lens", ROWS);
   const int* tp = a.as<int>(tiles, "tiles", CONTIG, {ANY, 2});
+  // per-row key limits (Gemma-3 image blocks): one absolute key position per row of q
+  const int* lp = nullptr;
+  if (limits.has_value()) {
+    TORCH_CHECK(softcap == 0, "prefill_attention: limits with softcap > 0 has no kernel");
+    TORCH_CHECK(D == 128 || D == 256, "prefill_attention: limits need head_dim 128 or 256, got ", D);
+    lp = a.as<int>(*limits, "limits", CONTIG, exactly(q.size(0)));
+  }
   hipserve::launch_prefill_attention(op, out.stride(0), qp, q.stride(0), kv.k, kv.v, bt, block_tables.stride(0), cu, cl,
                                      tp, tiles.size(0), nq, nkv, D, kv.bs, (float)scale, (int)window, cur_stream(),
-                                     kv.f8, (float)softcap);
+                                     kv.f8, (float)softcap, lp);
 }
 
 // Per-head RMSNorm of q and k inside the merged qkv rows, in place (Qwen3 / Gemma-3).
@@ -1324,7 +1331,7 @@ void gelu_(at::Tensor& x, bool tanh_approx) {
   hipserve::launch_gelu(xp, x.numel(), tanh_approx, cur_stream());
 }
 
-void vision_attention(at::Tensor& out, at::Tensor& qkv, const at::Tensor& cos_sin, const at::Tensor& cu,
+void vision_attention(at::Tensor& out, at::Tensor& qkv, const c10::optional<at::Tensor>& cos_sin, const at::Tensor& cu,
                       const at::Tensor& tiles, int64_t nh, int64_t D, double scale) {
   Args a("vision_attention", qkv, "qkv");
   TORCH_CHECK(D == 16 || D == 64 || D == 72 || D == 80 || D == 96 || D == 128,
@@ -1332,10 +1339,26 @@ void vision_attention(at::Tensor& out, at::Tensor& qkv, const at::Tensor& cos_si
   void* qp = a.ptr(qkv, "qkv", BF16, CONTIG, {ANY, 3 * nh * D});
   const int T = qkv.size(0);
   void* op = a.ptr(out, "out", BF16, CONTIG, {T, nh * D});
-  const float* cs = a.as<float>(cos_sin, "cos_sin", CONTIG, {at_least(T), D});
+  // no table: no RoPE (SigLIP)
+  const float* cs = cos_sin.has_value() ? a.as<float>(*cos_sin, "cos_sin", CONTIG, {at_least(T), D}) : nullptr;
   const int* cup = a.as<int>(cu, "cu", CONTIG);
   const int* tp = a.as<int>(tiles, "tiles", CONTIG, {ANY, 2});
   hipserve::launch_vision_attention(op, qp, cs, cup, tp, tiles.size(0), T, nh, D, (float)scale, cur_stream());
+}
+
+// Gemma-3 projector front: k x k average pool of each image's g x g patch rows + RMSNorm (1 + w)
+void vision_pool_rmsnorm(at::Tensor& out, const at::Tensor& x, const at::Tensor& w, int64_t g, int64_t k, double eps) {
+  Args a("vision_pool_rmsnorm", x, "x");
+  TORCH_CHECK(g > 0 && k > 0 && g % k == 0, "vision_pool_rmsnorm: the pool size k must divide the grid side g");
+  const void* xp = a.ptr(x, "x", BF16, CONTIG, {ANY, ANY});
+  const int64_t C = x.size(1);
+  TORCH_CHECK(C % 8 == 0 && C <= 4096, "vision_pool_rmsnorm: C must be a multiple of 8, <= 4096");
+  TORCH_CHECK(x.size(0) % (g * g) == 0, "vision_pool_rmsnorm: x must hold whole images of g * g rows");
+  const int64_t images = x.size(0) / (g * g);
+  TORCH_CHECK(x.size(0) < (1L << 31), "vision_pool_rmsnorm: too many rows");
+  void* op = a.ptr(out, "out", BF16, CONTIG, {images * (g / k) * (g / k), C});
+  const void* wp = a.ptr(w, "w", BF16, CONTIG, exactly(C));
+  hipserve::launch_vision_pool_rmsnorm(op, xp, wp, (int)images, (int)g, (int)k, (int)C, (float)eps, cur_stream());
 }
 
 }  // namespace
@@ -1358,7 +1381,7 @@ void vision_attention(at::Tensor& out, at::Tensor& qkv, const at::Tensor& cos_si
   X(silu_and_mul, "(Tensor(a!) out, Tensor x) -> ()") \
   X(rope_cache, "(Tensor(a!) qkv, Tensor positions, Tensor slots, Tensor cos_sin, Tensor(b!) k_cache, Tensor(c!) v_cache, int nq, int nkv, int head_dim, int mode) -> ()") \
   X(paged_decode, "(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor context_lens, Tensor(b!) tmp_out, Tensor(c!) tmp_ml, int nq, int nkv, int part_size, float scale, int window=0, Tensor(d!)? out16=None, float softcap=0.0) -> ()") \
-  X(prefill_attention, "(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor cu_q, Tensor ctx_lens, Tensor tiles, int nq, int nkv, float scale, int window=0, float softcap=0.0) -> ()") \
+  X(prefill_attention, "(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor cu_q, Tensor ctx_lens, Tensor tiles, int nq, int nkv, float scale, int window=0, float softcap=0.0, Tensor? limits=None) -> ()") \
   X(qk_rmsnorm, "(Tensor(a!) qkv, Tensor q_w, Tensor k_w, int nq, int nkv, int head_dim, float eps) -> ()") \
   X(gelu_and_mul, "(Tensor(a!) out, Tensor x) -> ()") \
   X(gguf_gemm, "(Tensor(a!) out, Tensor x, Tensor q, Tensor d, Tensor m, int qtype, int row_bytes, int N, int K, Tensor(b!) ws, int splits) -> ()") \
@@ -1390,7 +1413,8 @@ void vision_attention(at::Tensor& out, at::Tensor& qkv, const at::Tensor& cos_si
   X(top_logprobs, "(Tensor logits, Tensor nreq, Tensor(a!) out_ids, Tensor(b!) out_lp) -> ()") \
   X(layernorm, "(Tensor(a!) out, Tensor x, Tensor w, Tensor b, Tensor(b!)? residual, float eps) -> ()") \
   X(gelu_, "(Tensor(a!) x, bool tanh_approx) -> ()") \
-  X(vision_attention, "(Tensor(a!) out, Tensor(b!) qkv, Tensor cos_sin, Tensor cu, Tensor tiles, int nh, int D, float scale) -> ()") \
+  X(vision_pool_rmsnorm, "(Tensor(a!) out, Tensor x, Tensor w, int g, int k, float eps) -> ()") \
+  X(vision_attention, "(Tensor(a!) out, Tensor(b!) qkv, Tensor? cos_sin, Tensor cu, Tensor tiles, int nh, int D, float scale) -> ()") \
   X(sample, "(Tensor(a!) out_tok, Tensor(b!) out_lp, Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds, Tensor steps, bool two_rounds=True, Tensor? min_p=None) -> ()")
 
 TORCH_LIBRARY(hipserve, m) {

@@ -22,7 +22,14 @@ class VisionConfig:
     """Qwen3-VL vision tower (HF ``vision_config``): a ViT over 16x16x2 (HxWxT)
     patches with a learned, bilinearly resampled position table, 2D RoPE, a 2x2
     spatial merger into the language model's hidden size and DeepStack features
-    (merged outputs of intermediate blocks added to the first decoder layers)."""
+    (merged outputs of intermediate blocks added to the first decoder layers).
+
+    ``kind == "siglip"``: Gemma-3's SigLIP tower (HF ``siglip_vision_model``) — a fixed
+    ``image_size`` square cut into ``patch_size`` patches (no temporal axis, no RoPE, no
+    resampling of the position table), whose patch grid the projector average-pools to
+    ``mm_tokens_per_image`` tokens; ``image_token_id`` / ``vision_start_token_id`` /
+    ``vision_end_token_id`` hold Gemma's ``image_token_index`` / ``boi`` / ``eoi``."""
+    kind: str = "qwen3_vl"               # qwen3_vl | siglip
     depth: int = 27
     hidden_size: int = 1152
     intermediate_size: int = 4304
@@ -45,6 +52,20 @@ class VisionConfig:
     max_pixels: int = 16777216
     image_mean: tuple = (0.5, 0.5, 0.5)
     image_std: tuple = (0.5, 0.5, 0.5)
+    # siglip only
+    image_size: int = 0
+    mm_tokens_per_image: int = 0
+    layer_norm_eps: float = 1e-6
+
+    @property
+    def grid(self) -> int:
+        """siglip: patches per image side."""
+        return self.image_size // self.patch_size
+
+    @property
+    def pool(self) -> int:
+        """siglip: side of the projector's average-pool window."""
+        return self.grid // int(round(self.mm_tokens_per_image ** 0.5))
 
     @property
     def head_dim(self) -> int:
@@ -57,6 +78,8 @@ class VisionConfig:
     @staticmethod
     def from_hf_dict(d: dict) -> "VisionConfig | None":
         v = d.get("vision_config")
+        if isinstance(v, dict) and v.get("model_type") == "siglip_vision_model" and d.get("model_type") == "gemma3":
+            return VisionConfig._siglip_from_hf(d, v)
         if not isinstance(v, dict) or "depth" not in v:
             return None
         kw = {k: v[k] for k in ("depth", "hidden_size", "intermediate_size", "num_heads", "patch_size",
@@ -67,6 +90,46 @@ class VisionConfig:
             if d.get(k) is not None:
                 kw[k] = int(d[k])
         return VisionConfig(**kw)
+
+    @staticmethod
+    def _siglip_from_hf(d: dict, v: dict) -> "VisionConfig":
+        def top(*names, default):
+            for k in names:
+                if d.get(k) is not None:
+                    return int(d[k])
+            return default
+
+        dflt = SIGLIP_SO400M
+        kw = dict(depth=v.get("num_hidden_layers", dflt.depth), hidden_size=v.get("hidden_size", dflt.hidden_size),
+                  intermediate_size=v.get("intermediate_size", dflt.intermediate_size),
+                  num_heads=v.get("num_attention_heads", dflt.num_heads),
+                  patch_size=v.get("patch_size", dflt.patch_size), in_channels=v.get("num_channels", 3),
+                  image_size=v.get("image_size", dflt.image_size),
+                  hidden_act=v.get("hidden_act", dflt.hidden_act),
+                  layer_norm_eps=float(v.get("layer_norm_eps", dflt.layer_norm_eps)),
+                  out_hidden_size=(d.get("text_config") or {}).get("hidden_size", 0),
+                  mm_tokens_per_image=top("mm_tokens_per_image", default=dflt.mm_tokens_per_image),
+                  image_token_id=top("image_token_index", "image_token_id", default=dflt.image_token_id),
+                  vision_start_token_id=top("boi_token_index", "boi_token_id", default=dflt.vision_start_token_id),
+                  vision_end_token_id=top("eoi_token_index", "eoi_token_id", default=dflt.vision_end_token_id))
+        c = dataclasses.replace(dflt, **kw)
+        c = dataclasses.replace(c, num_position_embeddings=c.grid * c.grid)
+        side = int(round(c.mm_tokens_per_image ** 0.5))
+        if (c.image_size % c.patch_size or side * side != c.mm_tokens_per_image or side == 0 or c.grid % side
+                or c.hidden_size % c.num_heads):
+            raise ValueError(f"unsupported SigLIP geometry: image {c.image_size}, patch {c.patch_size}, "
+                             f"{c.mm_tokens_per_image} tokens per image")
+        return c
+
+
+# Gemma-3 4B / 12B / 27B vision side: SigLIP-so400m at 896 x 896 (patch 14: a 64 x 64 grid,
+# pooled 4 x 4 to 256 tokens) and the published special-token ids. No config.json can be read
+# offline: these are the values published with the checkpoints, not read from one.
+SIGLIP_SO400M = VisionConfig(kind="siglip", depth=27, hidden_size=1152, intermediate_size=4304, num_heads=16,
+                             patch_size=14, temporal_patch_size=1, spatial_merge_size=1, out_hidden_size=0,
+                             num_position_embeddings=4096, deepstack_visual_indexes=(), image_size=896,
+                             mm_tokens_per_image=256, layer_norm_eps=1e-6, image_token_id=262144,
+                             vision_start_token_id=255999, vision_end_token_id=256000)
 
 
 @dataclass(frozen=True)
@@ -141,12 +204,14 @@ class ModelConfig:
     def from_hf_dict(d: dict, name: str = "model") -> "ModelConfig":
         """HF ``config.json`` -> ModelConfig for the served families. Multimodal
         wrappers (Gemma3ForConditionalGeneration, Qwen3-VL-MoE) contribute their
-        ``text_config`` (the language model; vision towers are not served). Both the
+        ``text_config`` (the language model) and their ``vision_config`` (Qwen3-VL's
+        tower, Gemma-3's SigLIP tower). Both the
         Hub's ``rope_theta``/``rope_scaling`` keys and the newer ``rope_parameters``
         form (per layer type for Gemma-3) are read."""
         arch = (d.get("architectures") or ["LlamaForCausalLM"])[0]
         mtype = d.get("model_type", "")
-        vision = VisionConfig.from_hf_dict(d) if mtype.startswith("qwen3_vl") or "qwen3vl" in arch.lower() else None
+        vision = (VisionConfig.from_hf_dict(d)
+                  if mtype.startswith("qwen3_vl") or "qwen3vl" in arch.lower() or mtype == "gemma3" else None)
         if isinstance(d.get("text_config"), dict):  # multimodal wrapper: the language model
             td = dict(d["text_config"])
             for k in ("eos_token_id", "bos_token_id", "tie_word_embeddings"):
@@ -184,7 +249,9 @@ class ModelConfig:
         )
         if kw["partial_rotary_factor"] != 1.0:
             raise NotImplementedError("partial rotary embeddings are not supported")
-        if vision is not None:
+        if vision is not None and vision.kind == "siglip":  # Gemma-3: plain positions, no MRoPE
+            kw.update(vision=vision)
+        elif vision is not None:
             rp = d.get("rope_parameters") or d.get("rope_scaling") or {}
             sec = tuple(int(x) for x in (rp.get("mrope_section") or (24, 20, 20)))
             if rp.get("mrope_interleaved") is False:
@@ -302,6 +369,10 @@ def _gemma3(name: str, *, hidden_size: int, num_layers: int, sliding_window: int
                        rope_local_theta=1e4, bos_token_id=2, eos_token_id=(1, 106), **kw)
 
 
+def _siglip_for(hidden_size: int) -> VisionConfig:
+    return dataclasses.replace(SIGLIP_SO400M, out_hidden_size=hidden_size)
+
+
 def _gemma2(name: str, *, hidden_size: int, num_layers: int, head_dim: int = 256,
             query_pre_attn_scalar: int | None = None, **kw) -> ModelConfig:
     """Gemma-2 2B / 9B / 27B: sliding (4096) and global layers alternate from a sliding layer 0,
@@ -366,15 +437,16 @@ PRESETS: dict[str, ModelConfig] = {
                                hidden_act="gelu_tanh", sandwich_norm=True, norm_offset=True,
                                embed_scale=5376 ** 0.5, attn_scale=168 ** -0.5, sliding_window=1024,
                                layer_windows=tuple(1024 if (i + 1) % 6 else 0 for i in range(62)),
-                               rope_local_theta=1e4, bos_token_id=2, eos_token_id=(1, 106)),
-    # the smaller Gemma-3 text models: head_dim 256 (the 27B alone has 128), published config.json values
+                               rope_local_theta=1e4, bos_token_id=2, eos_token_id=(1, 106),
+                               vision=_siglip_for(5376)),
+    # the smaller Gemma-3 models (the 1B is text-only): head_dim 256 (the 27B alone has 128), published config.json values
     "gemma-3-1b": _gemma3("gemma-3-1b", hidden_size=1152, num_layers=26, num_heads=4, num_kv_heads=1,
                           intermediate_size=6912, sliding_window=512, max_position_embeddings=32768,
                           vocab_size=262144, rope_scaling=None),
     "gemma-3-4b": _gemma3("gemma-3-4b", hidden_size=2560, num_layers=34, num_heads=8, num_kv_heads=4,
-                          intermediate_size=10240),
+                          intermediate_size=10240, vision=_siglip_for(2560)),
     "gemma-3-12b": _gemma3("gemma-3-12b", hidden_size=3840, num_layers=48, num_heads=16, num_kv_heads=8,
-                           intermediate_size=15360),
+                           intermediate_size=15360, vision=_siglip_for(3840)),
     # Gemma-2: published config.json values (27B: head_dim 128, query_pre_attn_scalar = hidden / heads)
     "gemma-2-2b": _gemma2("gemma-2-2b", hidden_size=2304, num_layers=26, num_heads=8, num_kv_heads=4,
                           intermediate_size=9216),

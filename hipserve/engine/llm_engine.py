@@ -56,6 +56,17 @@ class LLMEngine:
         self.tp = tp or get_tp()
         self.cfg, self.model_cfg, self.tokenizer = prepare_model(cfg, self.tp, model_cfg)
         cfg = self.cfg
+        vcfg = self.model_cfg.vision
+        if vcfg is not None and vcfg.kind == "siglip":
+            # an image block is prefilled in one chunk (its rows see each other) and must lie
+            # inside the sliding layers' window (prefill_attention's one limit per row)
+            n = vcfg.mm_tokens_per_image
+            if cfg.max_num_batched_tokens < n:
+                raise ValueError(f"max_num_batched_tokens ({cfg.max_num_batched_tokens}) is below the {n} tokens "
+                                 "of one image, which are prefilled in one chunk")
+            if 0 < self.model_cfg.sliding_window < n:
+                raise ValueError(f"sliding_window ({self.model_cfg.sliding_window}) is below the {n} tokens of "
+                                 "one image: image tokens attend to each other across the whole image")
         self.runner = ModelRunner(cfg, self.model_cfg, self.tp)
         self.max_model_len = self.runner.max_model_len
         self.blocks = BlockManager(self.runner.usable_blocks, cfg.block_size, cfg.enable_prefix_caching)

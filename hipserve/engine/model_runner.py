@@ -555,6 +555,9 @@ class ModelRunner:
         (every TP rank runs the replicated vision tower on the same pixels)."""
         pos = np.array(inp.positions, dtype=np.int64, copy=True)
         rope_rows, rope_pos, images = [], [], []
+        # Gemma-3: rows inside an image block see the whole block (limits[row] = its last
+        # position, every other row its own position); built only when a block row is here
+        limits = None
         t = 0
         for s in seqs:
             mm = s.seq.mm
@@ -573,13 +576,22 @@ class ModelRunner:
                         lo, hi = max(ia, a), min(ib, b)
                         if lo < hi:
                             images.append((t + lo - a, lo - ia, hi - ia, im.pixels, tuple(im.grid), im.digest))
+                    for ia, ib in mm.blocks:
+                        lo, hi = max(ia, a), min(ib, b)
+                        if lo < hi:
+                            if hi != ib:
+                                raise RuntimeError("a prefill chunk ends inside an image block")
+                            if limits is None:
+                                limits = np.array(inp.positions[:inp.num_prefill_tokens], dtype=np.int32, copy=True)
+                            limits[t + lo - a:t + hi - a] = ib - 1
                 if s.end > npr:
                     k0 = max(s.start, npr)
                     pos[t + k0 - s.start:t + n] = np.arange(k0, s.end) + mm.delta
             t += n
         inp.positions = pos
-        if rope_rows or images:
+        if rope_rows or images or limits is not None:
             inp.extra["mm"] = {
+                "limits": limits,
                 "rope_rows": np.concatenate(rope_rows) if rope_rows else np.zeros(0, np.int64),
                 "rope_pos": np.concatenate(rope_pos, 1) if rope_pos else np.zeros((3, 0), np.int64),
                 "images": images}
@@ -686,6 +698,8 @@ class ModelRunner:
         from ..multimodal import mrope_cos_sin
 
         cfg = self.mcfg
+        if mm.get("limits") is not None:
+            meta.limits = self._t(mm["limits"])
         if len(mm["rope_rows"]):
             cs = self.model.cos_sin.index_select(0, meta.positions)
             rows = self._t(mm["rope_rows"])
@@ -701,12 +715,13 @@ class ModelRunner:
         uniq = {}
         for _, _, _, pixels, grid, digest in mm["images"]:
             uniq.setdefault(digest, (pixels, grid))
-        geo = image_geometry([g for _, g in uniq.values()], vis.cfg)
+        siglip = vis.cfg.kind == "siglip"  # fixed geometry: no resampling taps, no RoPE coordinates
+        geo = None if siglip else image_geometry([g for _, g in uniq.values()], vis.cfg)
         emb, ds_all = vis.forward(torch.from_numpy(np.concatenate([p for p, _ in uniq.values()])), geo)
         cache, off = {}, 0
         m2 = vis.cfg.spatial_merge_size ** 2
         for digest, (pixels, _) in uniq.items():
-            n = pixels.shape[0] // m2
+            n = vis.cfg.mm_tokens_per_image if siglip else pixels.shape[0] // m2
             cache[digest] = (emb[off:off + n], [d[off:off + n] for d in ds_all])
             off += n
         rows, embs, dss = [], [], []

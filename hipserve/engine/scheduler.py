@@ -7,6 +7,14 @@ sequence still in prefill), then newly admitted ones (their prompt minus any
 prefix-cache hit, chunked to the remaining budget). When the KV pool runs dry
 the most recently admitted running sequence is preempted (blocks freed, state
 reset to recompute) — FCFS fairness, no swap space needed with 288 GB HBM.
+
+Image blocks (Gemma-3: the tokens of one image attend to each other in both
+directions, ``Sequence.mm.blocks``): a prefill chunk never ends inside one, because
+the block's earlier rows need the later rows' keys. A chunk that would is trimmed
+back to the block's start; a chunk that starts at (or, after a prefix-cache hit,
+inside) a block takes the whole rest of it, and where the sequences ahead left less
+than that, the sequence waits one step with that much of the next step's budget
+held for it.
 """
 from __future__ import annotations
 
@@ -58,6 +66,26 @@ class Scheduler:
         self.waiting: deque[Sequence] = deque()
         self.running: list[Sequence] = []
         self.num_preemptions = 0
+        self._held: Sequence | None = None  # waits for a whole image block (module docstring)
+
+    @staticmethod
+    def _chunk(seq: Sequence, n: int) -> int:
+        """Tokens of ``seq``'s next prefill chunk given room for ``n``: ``n``, less where
+        the chunk would end inside an image block (0: the block it starts in needs more)."""
+        mm = seq.mm
+        if mm is None or not mm.blocks or n <= 0:
+            return max(n, 0)
+        start = seq.num_computed_tokens
+        a = mm.block_start(start + n)
+        return n if a == start + n else max(a - start, 0) if a > start else 0
+
+    @staticmethod
+    def _block_need(seq: Sequence) -> int:
+        """Tokens up to the end of the image block that ``seq``'s next chunk starts in."""
+        mm, start = seq.mm, seq.num_computed_tokens
+        if mm is None:
+            return 0
+        return max((b - start for a, b in mm.blocks if a <= start < b), default=0)
 
     def add(self, seq: Sequence):
         seq.status = Status.WAITING
@@ -98,11 +126,24 @@ class Scheduler:
         out = SchedulerOutput()
         budget = self.max_tokens
         scheduled_ids = set()
+        # the sequence that found no room for its image block last step: the others leave it that room
+        held, self._held, reserve = self._held, None, 0
+        if held is not None and (held in self.running or (
+                self.waiting and self.waiting[0] is held and len(self.running) < self.max_num_seqs)):
+            reserve = min(self._block_need(held), budget)
         # ---- 1. running sequences (FCFS order; victims taken from the tail)
         i = 0
         while i < len(self.running) and budget > 0:
             seq = self.running[i]
-            n = min(seq.num_uncomputed, budget) if seq.is_prefill else 1
+            room = budget if seq is held else budget - reserve
+            n = self._chunk(seq, min(seq.num_uncomputed, room)) if seq.is_prefill else min(1, room)
+            if n <= 0:  # this step has no room for it (the held room, or an image block that needs more)
+                if seq.is_prefill and room > 0 and self._held is None:
+                    self._held = seq
+                i += 1
+                continue
+            if seq is held:
+                reserve = 0
             target = seq.num_computed_tokens + n
             while not self.blocks.can_grow(seq, target):
                 victim = self.running[-1]
@@ -124,7 +165,14 @@ class Scheduler:
                 seq = self.waiting[0]
                 if seq.num_computed_tokens == 0 and not seq.block_ids:
                     self.blocks.match_prefix(seq)
-                n = min(seq.num_uncomputed, budget)
+                room = budget if seq is held else budget - reserve
+                n = self._chunk(seq, min(seq.num_uncomputed, room))
+                if n <= 0:  # no room this step: it stays first in line (its prefix hit kept)
+                    if room > 0 and self._held is None:
+                        self._held = seq
+                    break
+                if seq is held:
+                    reserve = 0
                 target = seq.num_computed_tokens + n
                 # the watermark protects RUNNING sequences' growth: with nothing running
                 # (and nothing admitted yet this step) it would only block admission

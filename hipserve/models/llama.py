@@ -61,6 +61,9 @@ class AttnMeta:
     mm_rows: torch.Tensor | None = None
     mm_embeds: torch.Tensor | None = None
     mm_deepstack: list | None = None
+    # Gemma-3 image blocks: int32 [num_prefill_tokens], the last key position each prefill row
+    # sees beyond its own (its block's end); None: plain causal prefill
+    limits: torch.Tensor | None = None
     # decode lookahead (model_runner): (src, tok) — row i's input id is tok[src[i]]
     # where src[i] >= 0 (the previous graph step's sampled id), else ids[i]
     id_src: tuple | None = None
@@ -197,8 +200,13 @@ class LlamaModel(MoEMixin):
         self.block_size_hint = 16  # KV block size (set by the runner)
         self.quant_linear = None  # set by the GGUF loader: callable(x, qweight) -> y
         self.fused_decode = True  # decode-only batches: split-K partials -> fused epilogues
-        self.visual = None        # models.vision.VisionTower (Qwen3-VL), replicated on every TP rank
-        if cfg.vision is not None:
+        # models.vision.VisionTower (Qwen3-VL) / models.siglip.SiglipTower (Gemma-3), replicated on every TP rank
+        self.visual = None
+        if cfg.vision is not None and cfg.vision.kind == "siglip":
+            from .siglip import SiglipTower
+
+            self.visual = SiglipTower(cfg.vision, self.device, dtype, ops)
+        elif cfg.vision is not None:
             from .vision import VisionTower
 
             self.visual = VisionTower(cfg.vision, self.device, dtype, ops)
@@ -757,7 +765,8 @@ class LlamaModel(MoEMixin):
                            kc, vc, nq, nkv, D, cfg.rope_mode)
             if Tp:
                 ops.prefill_attention(attn[:Tp], qkv[:Tp], kc, vc, meta.bt_prefill, meta.cu_q,
-                                      meta.ctx_prefill, meta.tiles, nq, nkv, self.scale, win, cfg.attn_softcap)
+                                      meta.ctx_prefill, meta.tiles, nq, nkv, self.scale, win, cfg.attn_softcap,
+                                      meta.limits)
             if Td:  # rows past Tp + Td: prefill padding (model_runner._pad_rows)
                 ops.paged_decode(attn[Tp:Tp + Td], qkv[Tp:Tp + Td], kc, vc, meta.bt_decode, meta.ctx_decode,
                                  tmp_out, tmp_ml, nq, nkv, part, self.scale, win, None, cfg.attn_softcap)

@@ -1,4 +1,7 @@
-"""Image inputs of the OpenAI chat surface for the Qwen3-VL vision tower.
+"""Image inputs of the OpenAI chat surface for the Qwen3-VL vision tower and for
+Gemma-3's SigLIP tower (``VisionConfig.kind == "siglip"``: a fixed-size square image,
+bilinear resize, a fixed number of tokens per image, plain positions — the variants
+are noted at each function).
 
 * ``load_image``: an ``image_url`` content part (``data:`` URL with base64 payload,
   ``file://`` / local path when allowed, or http(s) with a timeout and size cap) ->
@@ -39,9 +42,12 @@ class ImageInput:
     pixels: np.ndarray      # fp32 [Np, patch_dim]
     grid: tuple             # (t, h, w) in patches
     digest: int             # content hash (prefix-cache key of the image tokens)
+    tokens: int = 0         # siglip: the fixed token count (mm_tokens_per_image); 0: from the grid
 
     @property
     def num_tokens(self) -> int:
+        if self.tokens:
+            return self.tokens
         t, h, w = self.grid
         return t * h * w // 4
 
@@ -61,16 +67,36 @@ class MMState:
     pos3: np.ndarray        # int64 [3, n_prompt] MRoPE positions
     delta: int              # rotary position of token i >= n_prompt is i + delta
     hash_ids: list          # prompt ids with image tokens replaced by content-keyed ids (< 0)
+    # Gemma-3: the spans whose tokens attend to each other in both directions inside the
+    # language model (a prefill chunk never ends inside one); empty for Qwen3-VL
+    blocks: tuple = ()
+
+    def block_end(self, i: int) -> int:
+        """End of the bidirectional block holding token i (exclusive), or i itself where
+        i is the first token of a block or in none: the nearest legal chunk end >= i."""
+        for a, b in self.blocks:
+            if a < i < b:
+                return b
+        return i
+
+    def block_start(self, i: int) -> int:
+        for a, b in self.blocks:
+            if a < i < b:
+                return a
+        return i
 
 
 def mm_state(ids: list[int], images: list, cfg: VisionConfig) -> MMState:
     spans = image_spans(ids, images, cfg)
-    pos3, delta = mrope_positions(len(ids), spans, images, cfg.spatial_merge_size)
+    if cfg.kind == "siglip":  # no MRoPE: every axis is the plain index
+        pos3, delta = np.broadcast_to(np.arange(len(ids), dtype=np.int64), (3, len(ids))), 0
+    else:
+        pos3, delta = mrope_positions(len(ids), spans, images, cfg.spatial_merge_size)
     hids = list(ids)
     for (a, b), im in zip(spans, images):
         for j in range(a, b):  # negative ids never collide with vocabulary ids
             hids[j] = -1 - ((im.digest + 0x9E3779B97F4A7C15 * (j - a + 1)) & 0x3FFFFFFF)
-    return MMState(images, spans, pos3, delta, hids)
+    return MMState(images, spans, pos3, delta, hids, tuple(spans) if cfg.kind == "siglip" else ())
 
 
 def load_image(url: str, allow_local: bool = False, timeout: float = 10.0):
@@ -130,9 +156,32 @@ def smart_resize(h: int, w: int, factor: int, min_pixels: int, max_pixels: int) 
     return hb, wb
 
 
+def _preprocess_siglip(img, cfg: VisionConfig) -> ImageInput:
+    """Gemma-3 (HF ``Gemma3ImageProcessor`` with pan-and-scan off, its default): RGB,
+    bilinear resize to image_size x image_size, 1/255, (x - mean) / std; patches row-major,
+    each flattened (channel, row, col) like the patch Conv2d's weight."""
+    from PIL import Image
+
+    S, p = cfg.image_size, cfg.patch_size
+    if min(img.size) <= 0:
+        raise ImageInputError("empty image")
+    img = img.convert("RGB")
+    if img.size != (S, S):
+        img = img.resize((S, S), resample=Image.BILINEAR)
+    a = np.asarray(img, dtype=np.uint8).astype(np.float32) * np.float32(1 / 255)
+    a = (a - np.asarray(cfg.image_mean, np.float32)) / np.asarray(cfg.image_std, np.float32)
+    g = cfg.grid
+    x = a.transpose(2, 0, 1).reshape(a.shape[2], g, p, g, p).transpose(1, 3, 0, 2, 4)  # gh gw C ph pw
+    pix = np.ascontiguousarray(x.reshape(g * g, -1), dtype=np.float32)
+    digest = int.from_bytes(hashlib.blake2b(pix.tobytes(), digest_size=8).digest(), "little")
+    return ImageInput(pix, (1, g, g), digest, cfg.mm_tokens_per_image)
+
+
 def preprocess_image(img, cfg: VisionConfig, max_pixels: int | None = None) -> ImageInput:
     from PIL import Image
 
+    if cfg.kind == "siglip":
+        return _preprocess_siglip(img, cfg)
     p, m, tp = cfg.patch_size, cfg.spatial_merge_size, cfg.temporal_patch_size
     W0, H0 = img.size
     H, W = smart_resize(H0, W0, p * m, cfg.min_pixels, max_pixels or cfg.max_pixels)

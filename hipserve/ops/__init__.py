@@ -94,9 +94,11 @@ class KernelOps:
         return out
 
     def prefill_attention(self, out, q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tiles,
-                          nq, nkv, scale, window=0, softcap=0.0):
+                          nq, nkv, scale, window=0, softcap=0.0, limits=None):
+        """limits: int32 [rows of q] or None; row r also sees the keys up to limits[r]
+        (absolute position; Gemma-3 image blocks attend in both directions)."""
         self._op.prefill_attention(out, q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tiles,
-                                   nq, nkv, scale, window, softcap)
+                                   nq, nkv, scale, window, softcap, limits)
         return out
 
     def sample(self, out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds=True,
@@ -148,8 +150,15 @@ class KernelOps:
         return (torch.from_numpy(cu.astype(np.int32)).to(dev), torch.from_numpy(tiles.reshape(-1, 2)).to(dev))
 
     def vision_attention(self, out, qkv, cos_sin, cu_seqlens, nh, D, scale, meta=None):
+        """cos_sin None: no RoPE (SigLIP)."""
         cu, tiles = meta
         self._op.vision_attention(out, qkv, cos_sin, cu, tiles, nh, D, scale)
+        return out
+
+    def vision_pool_rmsnorm(self, out, x, w, g, k, eps):
+        """x [images * g * g, C] in patch order -> out [images * (g/k)^2, C]: k x k average
+        pool + Gemma RMSNorm (1 + w) (the Gemma-3 projector ahead of its GEMM)."""
+        self._op.vision_pool_rmsnorm(out, x, w, g, k, eps)
         return out
 
 
@@ -196,11 +205,11 @@ class ReferenceOps:
         return out
 
     def prefill_attention(self, out, q, k_cache, v_cache, block_tables, cu_q, ctx_lens, tiles,
-                          nq, nkv, scale, window=0, softcap=0.0):
+                          nq, nkv, scale, window=0, softcap=0.0, limits=None):
         D = k_cache.shape[3]
         T = int(cu_q[-1])
-        out[:T, : nq * D].copy_(ref.prefill_attention(q, k_cache, v_cache, block_tables, cu_q,
-                                                      ctx_lens, nq, nkv, scale, window, softcap).view(T, nq * D))
+        out[:T, : nq * D].copy_(ref.prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nq, nkv,
+                                                      scale, window, softcap, limits).view(T, nq * D))
         return out
 
     def penalty_apply(self, logits, slot, pres, freq, rep, counts, seen):
@@ -236,8 +245,13 @@ class ReferenceOps:
         return x
 
     def vision_attention(self, out, qkv, cos_sin, cu_seqlens, nh, D, scale, meta=None):
-        ref.vision_rope(qkv, cos_sin, nh, D)
+        if cos_sin is not None:
+            ref.vision_rope(qkv, cos_sin, nh, D)
         out.copy_(ref.vision_attention(qkv, cu_seqlens, nh, D, scale))
+        return out
+
+    def vision_pool_rmsnorm(self, out, x, w, g, k, eps):
+        out.copy_(ref.vision_pool_rmsnorm(x, w, g, k, eps))
         return out
 
     def sample(self, out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds=True,

@@ -83,6 +83,16 @@ def vision_attention(qkv: torch.Tensor, cu_seqlens, nh: int, D: int, scale: floa
     return out.view(T, nh * D).to(qkv.dtype)
 
 
+def vision_pool_rmsnorm(x: torch.Tensor, w: torch.Tensor, g: int, k: int, eps: float) -> torch.Tensor:
+    """x [images * g * g, C] in patch order -> [images * (g/k)^2, C]: k x k average pool of
+    each image's g x g grid, then RMSNorm with (1 + w) (fp32 math, one rounding to x.dtype)."""
+    C = x.shape[1]
+    go = g // k
+    p = x.float().view(-1, go, k, go, k, C).mean(dim=(2, 4)).reshape(-1, C)
+    y = p * torch.rsqrt(p.pow(2).mean(-1, keepdim=True) + eps) * (1.0 + w.float())
+    return y.to(x.dtype)
+
+
 def qk_rmsnorm(qkv: torch.Tensor, q_w: torch.Tensor, k_w: torch.Tensor, nq: int, nkv: int, D: int, eps: float):
     """In place: RMSNorm over head_dim of every q head (weight q_w) and k head (k_w)."""
     T = qkv.shape[0]
@@ -204,10 +214,14 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nq, nkv, scale
     return out
 
 
-def prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nq, nkv, scale, window=0, softcap=0.0):
+def prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nq, nkv, scale, window=0, softcap=0.0,
+                      limits=None):
     """q [T, nq*D (+extra)] -> out [T, nq, D]; causal over absolute positions;
     window > 0: keys within ``window - 1`` positions before the query.
-    softcap > 0: capped scores, capped before the masks."""
+    softcap > 0: capped scores, capped before the masks.
+    limits (int [T], absolute key positions): row r sees key kk iff
+    kk <= max(pos, limits[r]) and the window's lower bound on pos holds (Gemma-3: the rows
+    of an image block carry the block's last position, so they see each other)."""
     D = k_cache.shape[3]
     G = nq // nkv
     T = int(cu_q[-1])
@@ -224,7 +238,8 @@ def prefill_attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nq, nkv
         s = softcap_scores(torch.einsum("qhd,nhd->hqn", qs, kf) * scale, softcap)
         qpos = torch.arange(ctx - ql, ctx, device=q.device)[:, None]
         kpos = torch.arange(ctx, device=q.device)[None, :]
-        mask = kpos > qpos
+        top = qpos if limits is None else torch.maximum(qpos, limits[q0:q1].to(qpos.dtype)[:, None])
+        mask = kpos > top
         if window > 0:
             mask = mask | (kpos <= qpos - window)
         s = s.masked_fill(mask[None], float("-inf"))

@@ -82,7 +82,10 @@ class BaseTokenizer:
         Qwen3-VL chat template emits for it — and its URL is returned, in prompt order.
         The single ``<|image_pad|>`` per image is expanded by the caller once the
         image's patch grid is known. Text segments are tokenised separately around the
-        image markers, so tokenizers without these special tokens work too."""
+        image markers, so tokenizers without these special tokens work too.
+        Gemma-3 (``vision.kind == "siglip"``): the marker ids come from the vision config
+        and an image part becomes what the HF processor emits, ``"\n\n"`` boi image eoi
+        ``"\n\n"``, the two ``"\n\n"`` tokenised by this tokenizer."""
         urls: list[str] = []
         flat = []
         for m in messages:
@@ -104,10 +107,14 @@ class BaseTokenizer:
             flat.append(m)
         text = self.apply_chat_template(flat, True)
         pieces = text.split(_IMAGE_MARK)
+        mark = [vision.vision_start_token_id, vision.image_token_id, vision.vision_end_token_id]
+        if getattr(vision, "kind", "") == "siglip":
+            nl = self.encode("\n\n", add_special_tokens=False)
+            mark = nl + mark + nl
         ids = []
         for i, piece in enumerate(pieces):
             if i:
-                ids += [vision.vision_start_token_id, vision.image_token_id, vision.vision_end_token_id]
+                ids += mark
             if piece:
                 ids += self.encode(piece, add_special_tokens=False)
         if self.chat_adds_bos and self.bos_token_id is not None and self.add_bos \

@@ -410,7 +410,19 @@ def load_hf_weights(model: LlamaModel, model_path: str):
     if n_int4[0] or n_int4[1]:
         log.info("rank %d/%d: %d projections and %d expert stacks resident as tiled 4-bit chunks only "
                  "(INT4, %.3f GiB)", r, W, n_int4[0], n_int4[1], n_int4[2] / 2**30)
-    if model.visual is not None:  # Qwen3-VL vision tower (bf16 in every checkpoint, replicated)
+    if model.visual is not None and cfg.vision.kind == "siglip":
+        # Gemma-3: SigLIP tower + projector, bf16 also where the language model is FP8 / INT8 (the
+        # FP8-Dynamic export leaves them unquantised), replicated on every rank; under
+        # "vision_tower.vision_model." / "multi_modal_projector.", the same below "model.", or the
+        # tower straight below "vision_tower." (what transformers 5 writes)
+        vname = ck.find("embeddings.patch_embedding.weight")
+        pname = ck.find("multi_modal_projector.mm_input_projection_weight")
+        if vname is None or pname is None:
+            raise KeyError("vision config present but no vision_tower.* / multi_modal_projector.* "
+                           "tensors in the checkpoint")
+        model.visual.load(ck.full, vname[: -len("embeddings.patch_embedding.weight")],
+                          pname[: -len("mm_input_projection_weight")])
+    elif model.visual is not None:  # Qwen3-VL vision tower (bf16 in every checkpoint, replicated)
         vname = ck.find("patch_embed.proj.weight")
         if vname is None:
             raise KeyError("vision config present but no visual.patch_embed.proj.weight in the checkpoint")

@@ -175,6 +175,19 @@ def bench_prefill(ops):
                                                           1 / math.sqrt(D), 0, cap), n=10)
                 emit(op="prefill_attention", D=D, ver=ver, kv="fp8" if kvt == torch.float8_e4m3fn else "bf16", S=S,
                      nseq=nseq, nq=nq, nkv=nkv, softcap=cap, us=round(us, 1), TFLOPs=round(flops / us / 1e6, 1))
+            # BENCH_LIMITS=1: the per-row key limit kernels too (Gemma-3 image blocks), on the same
+            # tensors: one 256-token block per sequence at rows [S/2, S/2 + 256), and limits equal
+            # to every row's own position ("own": the limit kernel doing the causal kernel's work)
+            if os.environ.get("BENCH_LIMITS") == "1" and D in (128, 256) and ver != "v2w4":
+                own = torch.arange(S, device=DEV, dtype=torch.int32).repeat(nseq)
+                blk = own.clone().view(nseq, S)
+                blk[:, S // 2:S // 2 + 256] = S // 2 + 255
+                for name, lim in (("own", own), ("block256", blk.view(-1))):
+                    us = timeit(lambda: ops.prefill_attention(out, q, kc, vc, bt, cu, ctx, tiles, nq, nkv,
+                                                              1 / math.sqrt(D), 0, 0.0, lim), n=10)
+                    emit(op="prefill_attention", D=D, ver=ver, kv="fp8" if kvt == torch.float8_e4m3fn else "bf16",
+                         S=S, nseq=nseq, nq=nq, nkv=nkv, limits=name, us=round(us, 1),
+                         TFLOPs=round(flops / us / 1e6, 1))
         os.environ.pop("HIPSERVE_PREFILL_ATTN_V1", None)
 
 

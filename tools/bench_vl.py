@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--text-len", type=int, default=256)
     ap.add_argument("--output-len", type=int, default=256)
     ap.add_argument("--quantization", default=None, choices=[None, "int8", "fp8"])
+    ap.add_argument("--model", default="qwen3-vl-30b-a3b",
+                    help="a preset with a vision tower: qwen3-vl-30b-a3b, gemma-3-4b / -12b / -27b "
+                         "(Gemma-3 resizes every image to 896 x 896: --image-size only sets the source size)")
     a = ap.parse_args()
     import PIL.Image
 
@@ -37,7 +40,7 @@ def main():
     from hipserve.multimodal import MultiModalPrompt, expand_image_tokens, preprocess_image
 
     extra = {"quantization": a.quantization} if a.quantization else {}
-    eng = LLMEngine(EngineConfig(model="qwen3-vl-30b-a3b", load_format="dummy", device="cuda",
+    eng = LLMEngine(EngineConfig(model=a.model, load_format="dummy", device="cuda",
                                  max_num_seqs=a.requests, max_num_batched_tokens=8192, max_model_len=4096,
                                  extra=extra))
     vc = eng.model_cfg.vision
@@ -46,7 +49,7 @@ def main():
     for i in range(a.requests):
         img = preprocess_image(PIL.Image.fromarray(
             rng.integers(0, 256, (a.image_size, a.image_size, 3), dtype=np.uint8)), vc)
-        text = [int(t) for t in rng.integers(10, 150000, a.text_len)]
+        text = [int(t) for t in rng.integers(10, min(150000, vc.vision_start_token_id), a.text_len)]
         ids = expand_image_tokens([vc.vision_start_token_id, vc.image_token_id, vc.vision_end_token_id] + text,
                                   [img], vc)
         prompts.append(MultiModalPrompt(ids, [img]))
@@ -63,7 +66,7 @@ def main():
             n_out += len(o.new_token_ids)
     wall = time.perf_counter() - t0
     ttft = sorted(first.values())
-    print(json.dumps({"model": "qwen3-vl-30b-a3b" + (f" {a.quantization.upper()}" if a.quantization else ""),
+    print(json.dumps({"model": a.model + (f" {a.quantization.upper()}" if a.quantization else ""),
                       "requests": a.requests, "image": a.image_size, "image_tokens": prompts[0].images[0].num_tokens,
                       "prompt_tokens": len(prompts[0].ids), "output_len": a.output_len,
                       "wall_s": round(wall, 3), "output_tok_per_s": round(n_out / wall, 1),
