@@ -92,6 +92,13 @@ void launch_penalty_init(int* counts, unsigned int* seen, int V, const int* slot
 void launch_top_logprobs(const void* logits, bool is_bf16, long stride, int rows, int V, const int* nreq,
                          int* out_ids, float* out_lp, int K, hipStream_t s);
 
+// prompt_logprobs.hip — per scored prefill row: the target token's log-softmax and rank
+// (0 / -inf for a target outside [0, V)) and the nreq[row] <= K largest log-softmax entries,
+// ordered as top_logprobs orders them; rows with nreq <= 1 are read once
+void launch_prompt_logprobs(const void* logits, bool is_bf16, long stride, int rows, int V, const int* targets,
+                            const int* nreq, float* out_lp, int* out_rank, int* out_ids, float* out_top, int K,
+                            hipStream_t s);
+
 // gguf.hip (v1) — qtype: its own QT_* ids 0 Q4_0, 1 Q4_1, 2 Q8_0, 3 Q4_K, 4 Q5_K, 5 Q6_K (repacked
 // layouts); the tiled kernels of gguf_mfma.hip below take the ids of quant_formats.h
 void launch_gguf_gemm(void* out, float* ws, const void* x, long x_stride, long out_stride,

@@ -893,6 +893,22 @@ void top_logprobs(const at::Tensor& logits, const at::Tensor& nreq, at::Tensor& 
   hipserve::launch_top_logprobs(L.p, L.bf16, L.stride, L.rows, L.V, np, ip, lp, out_ids.size(1), cur_stream());
 }
 
+// per logits row: log-prob and rank of targets[row], and the nreq[row] largest log-probs
+void prompt_logprobs(const at::Tensor& logits, const at::Tensor& targets, const at::Tensor& nreq, at::Tensor& out_lp,
+                     at::Tensor& out_rank, at::Tensor& out_ids, at::Tensor& out_top) {
+  Args a("prompt_logprobs", logits, "logits");
+  const Logits L = logits_rows(a, logits);
+  const int* tp = a.as<int>(targets, "targets", CONTIG, exactly(L.rows));
+  const int* np = a.as<int>(nreq, "nreq", CONTIG, exactly(L.rows));
+  float* lp = a.as<float>(out_lp, "out_lp", CONTIG, exactly(L.rows));
+  int* rp = a.as<int>(out_rank, "out_rank", CONTIG, exactly(L.rows));
+  int* ip = a.as<int>(out_ids, "out_ids", CONTIG, {L.rows, ANY});
+  TORCH_CHECK(out_ids.size(1) <= 20, "prompt_logprobs: out_ids must have at most 20 per row, got ", out_ids.size(1));
+  float* vp = a.as<float>(out_top, "out_top", CONTIG, {L.rows, out_ids.size(1)});
+  hipserve::launch_prompt_logprobs(L.p, L.bf16, L.stride, L.rows, L.V, tp, np, lp, rp, ip, vp, out_ids.size(1),
+                                   cur_stream());
+}
+
 void fill_uniform(at::Tensor& out, int64_t row0, int64_t col0, int64_t gcols, int64_t key, double scale) {
   Args a("fill_uniform", out, "out");
   void* op = a.ptr(out, "out", BF16, ROWS, {ANY, ANY});
@@ -1411,6 +1427,7 @@ void vision_pool_rmsnorm(at::Tensor& out, const at::Tensor& x, const at::Tensor&
   X(penalty_update, "(Tensor tok, Tensor slot, Tensor(a!) counts, Tensor(b!) seen) -> ()") \
   X(penalty_init, "(Tensor(a!) counts, Tensor(b!) seen, Tensor slots, Tensor off, Tensor n_prompt, Tensor toks) -> ()") \
   X(top_logprobs, "(Tensor logits, Tensor nreq, Tensor(a!) out_ids, Tensor(b!) out_lp) -> ()") \
+  X(prompt_logprobs, "(Tensor logits, Tensor targets, Tensor nreq, Tensor(a!) out_lp, Tensor(b!) out_rank, Tensor(c!) out_ids, Tensor(d!) out_top) -> ()") \
   X(layernorm, "(Tensor(a!) out, Tensor x, Tensor w, Tensor b, Tensor(b!)? residual, float eps) -> ()") \
   X(gelu_, "(Tensor(a!) x, bool tanh_approx) -> ()") \
   X(vision_pool_rmsnorm, "(Tensor(a!) out, Tensor x, Tensor w, int g, int k, float eps) -> ()") \

@@ -19,7 +19,7 @@ from ..utils.faults import FaultInjector
 from ..utils.tracing import Tracer, step_kind
 from .block_manager import BlockManager
 from .metrics import EngineMetrics
-from .model_runner import ModelRunner
+from .model_runner import ModelRunner, prompt_logprob_span
 from .request import RequestOutput, SamplingParams, Sequence, Status
 from .scheduler import ScheduledSeq, Scheduler, SchedulerOutput
 
@@ -111,6 +111,9 @@ class LLMEngine:
             raise ValueError(f"prompt has {len(ids)} tokens; max_model_len is {self.max_model_len}")
         seq = Sequence(request_id, ids, params, eos_token_ids=self.eos_ids)
         vcfg = self.model_cfg.vision
+        if images and params.prompt_logprobs is not None:
+            # placeholder rows stand for image features: no token is their meaningful target
+            raise ValueError("prompt_logprobs is not supported for prompts with images")
         if images:
             if vcfg is None or self.runner.model.visual is None:
                 raise ValueError("this model has no vision encoder: image inputs are not supported")
@@ -179,7 +182,7 @@ class LLMEngine:
         now = time.monotonic()
         self._step_done(so, now - t0)
         with tr.phase("process"):
-            outputs += self._process(so, sampled, toks, lps, top, now)
+            outputs += self._process(so, sampled, toks, lps, top, now, inp.extra.pop("prompt_logprobs", None))
         return outputs
 
     def _step_done(self, so, dt):
@@ -261,8 +264,17 @@ class LLMEngine:
                 sampled.append((seq, len(seq.output_token_ids) - 1))
         return sampled
 
-    def _process(self, so, sampled, toks, lps, top, now):
+    def _process(self, so, sampled, toks, lps, top, now, plp=None):
         outputs = []
+        if plp is not None:  # this step's scored prompt rows, in prepare()'s order
+            lp, rank, ids, tl = (a.tolist() for a in plp)  # one conversion: a step scores thousands of rows
+            k = 0
+            for ss in so.prefill:
+                lo, hi = prompt_logprob_span(ss)
+                n = ss.seq.params.prompt_logprobs
+                ss.seq.prompt_logprobs.extend((lp[j], rank[j], list(zip(ids[j][:n], tl[j][:n])))
+                                              for j in range(k, k + hi - lo))
+                k += hi - lo
         for k, (seq, idx) in enumerate(sampled):
             if seq.status == Status.FINISHED or seq.request_id not in self.seqs:
                 continue  # finished / aborted while this step was in flight
@@ -315,6 +327,8 @@ class LLMEngine:
         out = RequestOutput(seq.request_id, [tok], text, reason is not None, reason,
                             seq.num_prompt_tokens, n_out, [lp] if top is None else [lp, top],
                             seq.output_text)
+        if n_out == 1 and p.prompt_logprobs is not None:  # nothing predicts the first prompt token
+            out.prompt_logprobs = [None] + seq.prompt_logprobs
         if reason is not None:
             del seq.output_token_ids[n_out:]  # drop a look-ahead placeholder
             del seq.output_logprobs[n_out:]
@@ -349,6 +363,25 @@ class LLMEngine:
                 if o.finished:
                     r[2] = o.finish_reason
         return [tuple(res[rid]) for rid in order]
+
+    def score(self, prompts, top_n: int = 0) -> list[np.ndarray]:
+        """Blocking batch scoring, the offline counterpart of ``generate``: per prompt the
+        log-probs (fp32, length ``len(prompt) - 1``) the model gives each prompt token after
+        the first, of the raw distribution. ``top_n`` alternatives per position are computed
+        too (the cost of a request with ``prompt_logprobs=top_n``) but not returned."""
+        order = []
+        for p in prompts:
+            sp = SamplingParams(temperature=0.0, max_tokens=1, ignore_eos=True, prompt_logprobs=top_n)
+            order.append(self.add_request(None, p, sp).request_id)
+        res = {}
+        while self.has_unfinished():
+            for o in self.step():
+                if o.prompt_logprobs is not None:
+                    res[o.request_id] = np.array([e[0] for e in o.prompt_logprobs[1:]], np.float32)
+        missing = [rid for rid in order if rid not in res]
+        if missing:
+            raise RuntimeError(f"score: {len(missing)} prompt(s) could not be scheduled (KV pool too small)")
+        return [res[rid] for rid in order]
 
     def shutdown(self):
         self.tracer.close()

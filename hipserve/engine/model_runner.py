@@ -31,6 +31,9 @@ from .scheduler import SchedulerOutput
 log = logging.getLogger("hipserve.runner")
 PREFILL_TILE = 128
 TOP_LOGPROBS = 20   # per-row capacity of the device top-logprobs output (OpenAI max)
+# prompt log-probs: the lm_head runs over the scored prefill rows in chunks whose bf16 logits
+# fit this many bytes (1,046 rows at a 128,256-entry vocabulary), so they never exist all at once
+PROMPT_LOGPROBS_CHUNK_BYTES = 256 << 20
 GPU_HEAD_DIMS = (64, 96, 128, 256)  # head sizes of the paged decode / prefill attention kernels
 GRAPH_BUCKETS = [1, 2, 4, 8, 16, 24, 32, 48, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384, 448, 512]
 
@@ -68,6 +71,23 @@ class StepInputs:
     min_p: np.ndarray | None = None       # float32 [n]: min_p per sampled row (0: off); None: all off
     bias_slot: np.ndarray | None = None   # int32 [n]: logit_bias slot per sampled row (-1: none)
     bias_init: tuple | None = None        # (slots, off, ids, vals): bias slots filled this step
+    # prompt log-probs (csrc/kernels/prompt_logprobs.hip): prefill rows scored against the
+    # NEXT prompt token, in batch order; None on a step that scores none
+    plp_rows: np.ndarray | None = None    # int64 [m]: rows of the batch
+    plp_targets: np.ndarray | None = None  # int32 [m]: the prompt token that follows each row
+    plp_n: np.ndarray | None = None       # int32 [m]: alternatives wanted per row (0: none)
+
+
+def prompt_logprob_span(ss) -> tuple[int, int]:
+    """Positions [lo, hi) of a prefill ``ScheduledSeq`` whose rows are scored this step:
+    inside the chunk, not scored before (a recompute after a preemption starts at 0
+    again), and below the last prompt position, which stays the sampling row. The target
+    of position p is prompt token p + 1, so a chunk boundary carries no state."""
+    q = ss.seq
+    if q.params.prompt_logprobs is None:
+        return 0, 0
+    lo, hi = max(ss.start, len(q.prompt_logprobs)), min(ss.end, q.num_prompt_tokens - 1)
+    return (lo, hi) if lo < hi else (0, 0)
 
 
 def pad_table(times: dict, tol: float = 1.03) -> dict:
@@ -457,7 +477,15 @@ class ModelRunner:
         rows = []
         t = 0
         sample_seqs = []
+        plp_rows, plp_tg, plp_n = [], [], []
         for s in so.prefill:
+            lo, hi = prompt_logprob_span(s)
+            if lo < hi:  # real rows of this chunk only: padding rows lie past Tp
+                if lo != len(s.seq.prompt_logprobs):
+                    raise RuntimeError("prompt log-probs: a chunk skips unscored positions (prefix hit?)")
+                plp_rows.extend(range(t + lo - s.start, t + hi - s.start))
+                plp_tg.extend(s.seq.prompt_token_ids[lo + 1:hi + 1])
+                plp_n.extend([min(s.seq.params.prompt_logprobs, TOP_LOGPROBS)] * (hi - lo))
             t += s.num_tokens
             if s.samples:
                 rows.append(t - 1)
@@ -543,6 +571,10 @@ class ModelRunner:
                          np.array(rows, dtype=np.int64), temp, topk, topp, seeds, steps,
                          pen_slot, pen_vals, nlp, pen_init, topn,
                          min_p=minp, bias_slot=bias_slot, bias_init=bias_init)
+        if plp_rows:
+            inp.plp_rows = np.array(plp_rows, np.int64)
+            inp.plp_targets = np.array(plp_tg, np.int32)
+            inp.plp_n = np.array(plp_n, np.int32)
         if any(s.seq.mm is not None for s in seqs):
             self._prepare_mm(seqs, inp)
         return inp
@@ -640,6 +672,7 @@ class ModelRunner:
         """Returns (tokens np.int64 [n], logprobs np.float32 [n], top_logprobs or None)."""
         n = len(inp.logits_rows)
         if self.graph_eligible(inp):
+            assert inp.plp_rows is None, "prompt log-probs belong to prefill steps, which run eagerly"
             return self.wait(self.launch(inp))
         if inp.src is not None:
             raise RuntimeError("device-side input ids (lookahead) need the hipGraph decode path")
@@ -658,6 +691,8 @@ class ModelRunner:
         if "mm" in inp.extra:
             self._attach_mm(inp.extra["mm"], meta, len(inp.ids))
         hidden = self.model.forward(ids, meta, self.kv)
+        if inp.plp_rows is not None:
+            inp.extra["prompt_logprobs"] = self._prompt_logprobs(hidden, inp)
         if n == 0:
             return np.zeros(0, np.int64), np.zeros(0, np.float32), None
         rows = self._t(inp.logits_rows)
@@ -687,6 +722,37 @@ class ModelRunner:
         if inp.top_logprobs:
             top = (ti.cpu().numpy(), tl.cpu().numpy())
         return tok.cpu().numpy(), lp.cpu().numpy(), top
+
+    def _prompt_logprobs(self, hidden, inp: StepInputs):
+        """Score the step's selected prefill rows: the lm_head in chunks of at most C rows
+        (``PROMPT_LOGPROBS_CHUNK_BYTES`` of bf16 logits, at least 16 rows) through the
+        unchanged ``compute_logits`` — packed / quantised heads, the TP all-gather, the
+        vocabulary slice and the final soft-cap all apply — then the one-pass kernel into
+        preallocated outputs, and ONE device-to-host copy after the last chunk. The log-probs
+        are of the raw model distribution (no logit_bias, no penalties), as top_logprobs'.
+        Returns (lp, rank, ids, top) numpy arrays on rank 0; TP workers run the same chunks
+        (the collectives are inside compute_logits) and return None."""
+        m = len(inp.plp_rows)
+        C = max(16, PROMPT_LOGPROBS_CHUNK_BYTES // (2 * self.mcfg.vocab_size))
+        rows, tg, nr = self._t(inp.plp_rows), self._t(inp.plp_targets), self._t(inp.plp_n)
+        lp = torch.empty(m, dtype=torch.float32, device=self.device)
+        rank = torch.empty(m, dtype=torch.int32, device=self.device)
+        ti = torch.empty(m, TOP_LOGPROBS, dtype=torch.int32, device=self.device)
+        tl = torch.empty(m, TOP_LOGPROBS, dtype=torch.float32, device=self.device)
+        for a in range(0, m, C):
+            b = min(a + C, m)
+            logits = self.model.compute_logits(hidden.index_select(0, rows[a:b]))
+            self.ops.prompt_logprobs(logits, tg[a:b], nr[a:b], lp[a:b], rank[a:b], ti[a:b], tl[a:b])
+            del logits
+        self.stats["prompt_logprob_rows"] = self.stats.get("prompt_logprob_rows", 0) + m
+        if not self.tp.is_first:
+            return None
+        if self.device.type != "cuda":
+            return lp.numpy(), rank.numpy(), ti.numpy(), tl.numpy()
+        packed = torch.cat([lp.view(m, 1), rank.view(torch.float32).view(m, 1), ti.view(torch.float32), tl], 1).cpu()
+        K = TOP_LOGPROBS
+        return (packed[:, 0].numpy(), packed[:, 1].contiguous().view(torch.int32).numpy(),
+                packed[:, 2:2 + K].contiguous().view(torch.int32).numpy(), packed[:, 2 + K:].numpy())
 
     def _attach_mm(self, mm: dict, meta: AttnMeta, T: int):
         """Vision-tower outputs and MRoPE rows of a multimodal prefill batch into the

@@ -84,6 +84,8 @@ class SamplingParams:
     n: int = 1
     min_p: float = 0.0          # keep tokens with p >= min_p * p_max (after top-k / top-p); 0: off
     logit_bias: object = None   # {token id: bias}; normalised to a sorted list of (id, bias)
+    # log-prob and rank of every prompt token plus this many alternatives (vLLM's field; 0: none)
+    prompt_logprobs: int | None = None
 
     def __post_init__(self):
         """Coerce and range-check every field: a value that reaches the engine
@@ -119,6 +121,8 @@ class SamplingParams:
         self.n = _int("n", self.n, 1, MAX_N)
         self.min_p = _float("min_p", self.min_p, 0.0, 1.0)
         self.logit_bias = _logit_bias(self.logit_bias)
+        if self.prompt_logprobs is not None:
+            self.prompt_logprobs = _int("prompt_logprobs", self.prompt_logprobs, 0, MAX_LOGPROBS)
 
     @property
     def greedy(self) -> bool:
@@ -164,6 +168,9 @@ class Sequence:
     pen_slot: int | None = None         # device penalty-state slot (ModelRunner), while it has penalties
     bias_slot: int | None = None        # device logit_bias slot (ModelRunner), while it has a bias
     mm: object = None                   # multimodal.MMState of a prompt with images
+    # params.prompt_logprobs: one (logprob, rank, [(id, logprob), ...]) per prompt position >= 1,
+    # in order; its length is the number of positions scored so far (kept across a preemption)
+    prompt_logprobs: list = field(default_factory=list)
     # detokenizer state
     output_text: str = ""
     _decoded_upto: int = 0
@@ -184,6 +191,13 @@ class Sequence:
     def token_at(self, i: int) -> int:
         n = len(self.prompt_token_ids)
         return self.prompt_token_ids[i] if i < n else self.output_token_ids[i - n]
+
+    @property
+    def wants_prompt_logprobs(self) -> bool:
+        """Prompt positions still to be scored: their rows need hidden states, so the
+        sequence takes no prefix-cache hit until the list is complete."""
+        return (self.params.prompt_logprobs is not None
+                and len(self.prompt_logprobs) < len(self.prompt_token_ids) - 1)
 
     @property
     def num_uncomputed(self) -> int:
@@ -211,3 +225,5 @@ class RequestOutput:
     num_output_tokens: int = 0
     logprobs: list[float] | None = None
     text: str = ""
+    # with the sequence's first generated token: None, then (logprob, rank, top list) per prompt token
+    prompt_logprobs: list | None = None

@@ -163,7 +163,8 @@ class Scheduler:
         if not out.preempted:
             while self.waiting and budget > 0 and len(self.running) < self.max_num_seqs:
                 seq = self.waiting[0]
-                if seq.num_computed_tokens == 0 and not seq.block_ids:
+                # cached positions have no hidden states to score: no hit while prompt log-probs are incomplete
+                if seq.num_computed_tokens == 0 and not seq.block_ids and not seq.wants_prompt_logprobs:
                     self.blocks.match_prefix(seq)
                 room = budget if seq is held else budget - reserve
                 n = self._chunk(seq, min(seq.num_uncomputed, room))

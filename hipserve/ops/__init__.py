@@ -128,6 +128,11 @@ class KernelOps:
     def top_logprobs(self, logits, nreq, out_ids, out_lp):
         self._op.top_logprobs(logits, nreq, out_ids, out_lp)
 
+    def prompt_logprobs(self, logits, targets, nreq, out_lp, out_rank, out_ids, out_top):
+        """Per row: log-prob and rank of targets[row] and the nreq[row] largest log-probs
+        (csrc/kernels/prompt_logprobs.hip)."""
+        self._op.prompt_logprobs(logits, targets, nreq, out_lp, out_rank, out_ids, out_top)
+
     # ---- vision tower (csrc/kernels/vision.hip)
     def layernorm(self, out, x, w, b, eps, residual=None):
         self._op.layernorm(out, x, w, b, residual, eps)
@@ -229,6 +234,9 @@ class ReferenceOps:
 
     def top_logprobs(self, logits, nreq, out_ids, out_lp):
         ref.top_logprobs(logits, nreq, out_ids, out_lp)
+
+    def prompt_logprobs(self, logits, targets, nreq, out_lp, out_rank, out_ids, out_top):
+        ref.prompt_logprobs(logits, targets, nreq, out_lp, out_rank, out_ids, out_top)
 
     # ---- vision tower (Qwen3-VL ViT)
     def layernorm(self, out, x, w, b, eps, residual=None):

@@ -449,3 +449,27 @@ def top_logprobs(logits, nreq, out_ids, out_lp):
         for i, v in enumerate(order):
             out_ids[r, i] = v
             out_lp[r, i] = ls[v]
+
+
+def prompt_logprobs(logits, targets, nreq, out_lp, out_rank, out_ids, out_top):
+    """Per row: the log-softmax and rank of ``targets[row]`` and the ``nreq[row]`` largest
+    log-softmax entries (the exact CPU form of csrc/kernels/prompt_logprobs.hip).
+
+    rank = 1 + #{v : l[v] > l[t]} + #{v < t : l[v] == l[t]} on the exact input values:
+    the target's index + 1 in the order (value desc, id asc) that the top list uses, so
+    rank <= n exactly when the target is entry rank - 1 of the top-n. A target outside
+    [0, V) gives -inf / 0. The top lists are ``top_logprobs``' above, with the same single
+    bound on the device kernel's exactness (more than 64 logits in the bf16 bin of the n-th
+    largest, rows with n >= 2 only: n <= 1 rows are exact on the device too)."""
+    V = logits.shape[1]
+    top_logprobs(logits, nreq, out_ids, out_top)
+    for r in range(logits.shape[0]):
+        t = int(targets[r])
+        if not 0 <= t < V:
+            out_lp[r] = float("-inf")
+            out_rank[r] = 0
+            continue
+        l = logits[r].float()
+        lt = l[t]
+        out_lp[r] = float("-inf") if lt == float("-inf") else lt - torch.logsumexp(l, 0)
+        out_rank[r] = 1 + int((l > lt).sum()) + int((l[:t] == lt).sum())

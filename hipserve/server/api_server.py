@@ -23,7 +23,7 @@ from aiohttp import web
 from prometheus_client import CONTENT_TYPE_LATEST, generate_latest
 
 from .. import __version__
-from ..engine.request import SamplingParams
+from ..engine.request import MAX_LOGPROBS, SamplingParams
 from ..utils.faults import stall_timeout
 from .async_engine import AsyncEngine, EngineDeadError
 
@@ -38,6 +38,12 @@ def _err(status: int, msg: str, typ: str = "invalid_request_error", code=None):
 
 def _dumps(o) -> str:
     return json.dumps(o, separators=(",", ":"), ensure_ascii=False)
+
+
+def _lp(v: float):
+    """A log-prob as JSON: -inf (a masked logit) has no JSON form; -9999 stands for it, as in
+    vLLM. NaN marks a prompt that was never scored: null."""
+    return max(float(v), -9999.0) if v == v else None
 
 
 def _has_images(msgs) -> bool:
@@ -148,6 +154,28 @@ class OpenAIServer:
         self._check_bias(params)
         return params
 
+    @staticmethod
+    def _scoring(body, params: SamplingParams, chat: bool):
+        """Prompt scoring fields: vLLM's ``prompt_logprobs`` (both endpoints) and OpenAI's
+        ``echo`` (completions). Returns (echo, the request's own prompt_logprobs or None) for
+        the handler and sets the engine field to the larger of that and, for echo with
+        ``logprobs``, the logprobs count: one pass over the prompt serves both. echo without
+        logprobs only prepends the prompt text and scores nothing."""
+        plp = body.get("prompt_logprobs")
+        if plp is not None and (isinstance(plp, bool) or not isinstance(plp, int)):
+            raise ValueError("prompt_logprobs must be an integer")
+        if plp is not None and not 0 <= plp <= MAX_LOGPROBS:
+            raise ValueError(f"prompt_logprobs must be in [0, {MAX_LOGPROBS}]")
+        echo = body.get("echo")
+        if echo is not None and not isinstance(echo, bool):
+            raise ValueError("echo must be a boolean")
+        echo = bool(echo) and not chat
+        want = plp
+        if echo and params.logprobs is not None:
+            want = max(params.logprobs, plp or 0)
+        params.prompt_logprobs = want  # logprobs is range-checked already
+        return echo, plp
+
     def _check_bias(self, params: SamplingParams):
         """logit_bias ids outside the vocabulary: a 400 before any SSE header goes out,
         as for prompt ids."""
@@ -186,6 +214,36 @@ class OpenAIServer:
                              f"but the prompt has {n_prompt} tokens.")
         params.max_tokens = min(params.max_tokens, room)
 
+    # ------------------------------------------------------------ prompt log-probs
+    def _vllm_prompt_logprobs(self, ids, plp, k: int):
+        """vLLM's ``prompt_logprobs``: null, then per prompt token {token id as a string:
+        {"logprob", "rank", "decoded_token"}} of the token itself plus the top k."""
+        if plp is None:  # the request ended before its first token (no room in the KV pool)
+            return None
+        out = [None]
+        for t, (lp, rank, top) in zip(ids[1:], plp[1:]):
+            d = {str(t): {"logprob": _lp(lp), "rank": rank, "decoded_token": self.tokenizer.decode([t])}}
+            for j, (i, v) in enumerate(top[:k]):  # the top list's order is the rank's order
+                d.setdefault(str(i), {"logprob": _lp(v), "rank": j + 1, "decoded_token": self.tokenizer.decode([i])})
+            out.append(d)
+        return out
+
+    def _echo_logprobs(self, ids, plp, k: int, gen_toks, gen_lps, gen_tops):
+        """OpenAI ``logprobs`` object of an echoed completion: prompt tokens first (nothing
+        predicts the first one: null), then the generated ones."""
+        dec = self.tokenizer.decode
+        if plp is None:  # the request ended before its first token: an unscored prompt
+            plp = [None] + [(float("nan"), 0, [])] * (len(ids) - 1)
+        tokens = [dec([t]) for t in ids] + [dec([t]) for t in gen_toks]
+        token_lps = [None] + [_lp(e[0]) for e in plp[1:]] + [_lp(v) for v in gen_lps]
+        tops = [None] + [{dec([i]): _lp(v) for i, v in e[2][:k]} for e in plp[1:]]
+        tops += [{dec([i]): _lp(v) for i, v in (top or [])[:k]} for top in gen_tops]
+        offs, o = [], 0
+        for t in tokens:
+            offs.append(o)
+            o += len(t)
+        return {"tokens": tokens, "token_logprobs": token_lps, "top_logprobs": tops, "text_offset": offs}
+
     async def _run_many(self, prompts, params: SamplingParams, base_id):
         """Fan out prompts x n into engine requests; returns list of (index, gen)."""
         gens = []
@@ -195,7 +253,9 @@ class OpenAIServer:
                 sp = params
                 if params.n > 1:
                     seed = None if params.seed is None else ((params.seed + j + (1 << 63)) % (1 << 64)) - (1 << 63)
-                    sp = SamplingParams(**{**params.__dict__, "n": 1, "seed": seed})
+                    # the prompt is scored once, in the first request; the handler copies the result
+                    sp = SamplingParams(**{**params.__dict__, "n": 1, "seed": seed,
+                                           "prompt_logprobs": params.prompt_logprobs if j == 0 else None})
                 gens.append((idx, self.ae.generate(f"{base_id}-{idx}", p, sp)))
                 idx += 1
         return gens
@@ -223,8 +283,9 @@ class OpenAIServer:
             return bad
         try:
             params = self._params(body, chat=False)
-            prompts = [self.tokenizer.encode(p) if isinstance(p, str) else list(p)
-                       for p in self._prompts(body)]
+            echo, plp_k = self._scoring(body, params, chat=False)
+            raw = self._prompts(body)
+            prompts = [self.tokenizer.encode(p) if isinstance(p, str) else list(p) for p in raw]
             for p in prompts:
                 self._check_prompt(p)
                 self._clip_max_tokens(params, len(p))
@@ -236,6 +297,10 @@ class OpenAIServer:
         stream = bool(body.get("stream", False))
         include_usage = bool((body.get("stream_options") or {}).get("include_usage", False))
         n_prompt_total = sum(len(p) for p in prompts) * params.n
+        scored = params.prompt_logprobs is not None
+        echo_lp = echo and params.logprobs is not None  # the logprobs object covers the prompt too
+        # echo: the prompt's text ahead of the completion (a token-id prompt is detokenised)
+        ptext = [p if isinstance(p, str) else self.tokenizer.decode(list(p)) for p in raw] if echo else None
         gens = await self._run_many(prompts, params, rid)
         if stream:
             resp = web.StreamResponse(headers={"Content-Type": "text/event-stream",
@@ -249,19 +314,43 @@ class OpenAIServer:
                 _dumps(rid), created, _dumps(model))
             try:
                 async with contextlib.aclosing(_merge(gens)) as merged:
-                    async for idx, o in merged:
-                        n_out += len(o.new_token_ids)
-                        if params.logprobs is not None and o.logprobs:
-                            ch = {"index": idx, "text": o.new_text, "finish_reason": o.finish_reason if o.finished else None,
-                                  "logprobs": {"tokens": [self.tokenizer.decode(o.new_token_ids)],
-                                               "token_logprobs": [o.logprobs[0]]}}
+                    if echo or scored:  # the first chunk of each choice carries the prompt part
+                        started = set()
+                        src = _with_prompt_logprobs(merged, params.n) if scored else ((i, o, None) async for i, o in merged)
+                        async for idx, o, plp in src:
+                            n_out += len(o.new_token_ids)
+                            first = idx not in started
+                            started.add(idx)
+                            ids = prompts[idx // params.n]
+                            ch = {"index": idx, "text": (ptext[idx // params.n] if echo and first else "") + o.new_text,
+                                  "logprobs": None, "finish_reason": o.finish_reason if o.finished else None}
+                            if params.logprobs is not None and o.logprobs:
+                                top = o.logprobs[1] if len(o.logprobs) > 1 else None
+                                if echo_lp and first:
+                                    ch["logprobs"] = self._echo_logprobs(ids, plp, params.logprobs, o.new_token_ids,
+                                                                         [o.logprobs[0]], [top])
+                                else:
+                                    ch["logprobs"] = {"tokens": [self.tokenizer.decode(o.new_token_ids)],
+                                                      "token_logprobs": [o.logprobs[0]]}
+                            if plp_k is not None and first:
+                                ch["prompt_logprobs"] = self._vllm_prompt_logprobs(ids, plp, plp_k)
                             chunk = {"id": rid, "object": "text_completion", "created": created,
                                      "model": model, "choices": [ch]}
                             await resp.write(("data: " + _dumps(chunk) + "\n\n").encode())
-                            continue
-                        fin = _dumps(o.finish_reason) if o.finished else "null"
-                        await resp.write(f'{head}{idx},"text":{_dumps(o.new_text)},"logprobs":null,'
-                                         f'"finish_reason":{fin}}}]}}\n\n'.encode())
+                    else:
+                        async for idx, o in merged:
+                            n_out += len(o.new_token_ids)
+                            if params.logprobs is not None and o.logprobs:
+                                ch = {"index": idx, "text": o.new_text, "finish_reason": o.finish_reason if o.finished else None,
+                                      "logprobs": {"tokens": [self.tokenizer.decode(o.new_token_ids)],
+                                                   "token_logprobs": [o.logprobs[0]]}}
+                                chunk = {"id": rid, "object": "text_completion", "created": created,
+                                         "model": model, "choices": [ch]}
+                                await resp.write(("data: " + _dumps(chunk) + "\n\n").encode())
+                                continue
+                            fin = _dumps(o.finish_reason) if o.finished else "null"
+                            await resp.write(f'{head}{idx},"text":{_dumps(o.new_text)},"logprobs":null,'
+                                             f'"finish_reason":{fin}}}]}}\n\n'.encode())
                 if include_usage:
                     u = {"id": rid, "object": "text_completion", "created": created, "model": model,
                          "choices": [], "usage": _usage(n_prompt_total, n_out)}
@@ -279,12 +368,20 @@ class OpenAIServer:
             return _err(400, str(e))
         choices, n_out = [], 0
         for idx in sorted(results):
-            text, toks, reason, lps = results[idx]
+            text, toks, reason, lps, tops, plp = results[idx]
             n_out += len(toks)
-            ch = {"index": idx, "text": text, "logprobs": None, "finish_reason": reason}
+            g = idx // params.n
+            if scored:  # scored once, by the prompt's first request
+                plp = results[g * params.n][5]
+            ch = {"index": idx, "text": ptext[g] + text if echo else text, "logprobs": None, "finish_reason": reason}
             if params.logprobs is not None:
-                ch["logprobs"] = {"tokens": [self.tokenizer.decode([t]) for t in toks],
-                                  "token_logprobs": lps}
+                if echo_lp:
+                    ch["logprobs"] = self._echo_logprobs(prompts[g], plp, params.logprobs, toks, lps, tops)
+                else:
+                    ch["logprobs"] = {"tokens": [self.tokenizer.decode([t]) for t in toks],
+                                      "token_logprobs": lps}
+            if plp_k is not None:
+                ch["prompt_logprobs"] = self._vllm_prompt_logprobs(prompts[g], plp, plp_k)
             choices.append(ch)
         return web.json_response({"id": rid, "object": "text_completion", "created": created,
                                   "model": model, "choices": choices,
@@ -304,7 +401,10 @@ class OpenAIServer:
             return _err(400, "messages must be a non-empty list")
         try:
             params = self._params(body, chat=True)
+            _, plp_k = self._scoring(body, params, chat=True)
             vcfg = self.engine.model_cfg.vision
+            if plp_k is not None and _has_images(msgs):
+                raise ValueError("prompt_logprobs is not supported for prompts with images")
             if vcfg is not None and _has_images(msgs):
                 prompt = await self._encode_images(msgs, vcfg)
                 ids = prompt.ids
@@ -338,12 +438,21 @@ class OpenAIServer:
                 _dumps(rid), created, _dumps(model))
             try:
                 async with contextlib.aclosing(_merge(gens)) as merged:
-                    async for idx, o in merged:
-                        n_out += len(o.new_token_ids)
-                        delta = '{"content":%s}' % _dumps(o.new_text) if (o.new_text or not o.finished) else "{}"
-                        fin = _dumps(o.finish_reason) if o.finished else "null"
-                        await resp.write(f'{head}{idx},"delta":{delta},"logprobs":null,'
-                                         f'"finish_reason":{fin}}}]}}\n\n'.encode())
+                    if plp_k is not None:  # the first content chunk of each choice carries the prompt's scores
+                        async for idx, o, plp in _with_prompt_logprobs(merged, params.n):
+                            n_out += len(o.new_token_ids)
+                            ch = {"index": idx, "delta": {"content": o.new_text} if (o.new_text or not o.finished) else {},
+                                  "logprobs": None, "finish_reason": o.finish_reason if o.finished else None}
+                            if plp is not None:
+                                ch["prompt_logprobs"] = self._vllm_prompt_logprobs(ids, plp, plp_k)
+                            await resp.write(("data: " + _dumps({**base, "choices": [ch]}) + "\n\n").encode())
+                    else:
+                        async for idx, o in merged:
+                            n_out += len(o.new_token_ids)
+                            delta = '{"content":%s}' % _dumps(o.new_text) if (o.new_text or not o.finished) else "{}"
+                            fin = _dumps(o.finish_reason) if o.finished else "null"
+                            await resp.write(f'{head}{idx},"delta":{delta},"logprobs":null,'
+                                             f'"finish_reason":{fin}}}]}}\n\n'.encode())
                 if include_usage:
                     await resp.write(("data: " + _dumps({**base, "choices": [],
                                                          "usage": _usage(n_prompt, n_out)}) + "\n\n").encode())
@@ -360,13 +469,15 @@ class OpenAIServer:
             return _err(400, str(e))
         choices, n_out = [], 0
         for idx in sorted(results):
-            text, toks, reason, lps = results[idx]
+            text, toks, reason, lps, _, _ = results[idx]
             n_out += len(toks)
             ch = {"index": idx, "message": {"role": "assistant", "content": text},
                   "logprobs": None, "finish_reason": reason}
             if params.logprobs:
                 ch["logprobs"] = {"content": [{"token": self.tokenizer.decode([t]), "logprob": lp}
                                               for t, lp in zip(toks, lps)]}
+            if plp_k is not None:  # scored once, by the first request
+                ch["prompt_logprobs"] = self._vllm_prompt_logprobs(ids, results[0][5], plp_k)
             choices.append(ch)
         return web.json_response({"id": rid, "object": "chat.completion", "created": created,
                                   "model": model, "choices": choices,
@@ -418,14 +529,38 @@ async def _merge(gens):
             await g.aclose()
 
 
+async def _with_prompt_logprobs(merged, n: int):
+    """(index, output, prompt log-probs or None) from ``_merge``'s stream when the requests
+    score their prompt: the list rides on the first output of each prompt's FIRST request
+    (index divisible by n) and goes out with the first output of every choice of that prompt;
+    outputs of the other choices that come earlier wait for it."""
+    plp, held, seen = {}, {}, set()
+    async for idx, o in merged:
+        g = idx // n
+        if g not in plp:
+            if idx % n:
+                held.setdefault(g, []).append((idx, o))
+                continue
+            plp[g] = o.prompt_logprobs  # None: it ended before its first token (no room in the KV pool)
+        for i, x in [(idx, o)] + held.pop(g, []):
+            yield i, x, (None if i in seen else plp[g])
+            seen.add(i)
+    for g in sorted(held):  # the first request never answered
+        for i, x in held[g]:
+            yield i, x, None
+
+
 async def _collect(gens):
     res = {}
     async for idx, o in _merge(gens):
-        r = res.setdefault(idx, ["", [], None, []])
+        r = res.setdefault(idx, ["", [], None, [], [], None])
         r[0] += o.new_text
         r[1].extend(o.new_token_ids)
         if o.logprobs:
             r[3].append(o.logprobs[0])
+            r[4].append(o.logprobs[1] if len(o.logprobs) > 1 else None)
+        if o.prompt_logprobs is not None:
+            r[5] = o.prompt_logprobs
         if o.finished:
             r[2] = o.finish_reason
     return {k: tuple(v) for k, v in res.items()}

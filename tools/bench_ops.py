@@ -3,6 +3,8 @@
 median of N launches). Prints one JSON line per case.
 
     python tools/bench_ops.py [sample|decode|prefill|gemm|norm|rope|all]
+    python tools/bench_ops.py prompt_logprobs        # the prompt-scoring kernel vs top_logprobs vs a copy
+    python tools/bench_ops.py prompt_logprobs_step   # cost of prompt_logprobs=1 to an 8 x 1,024 prefill step
 """
 import json
 import math
@@ -300,6 +302,95 @@ def bench_rope(ops):
     emit(op="paged_decode_qkv", B=B, ctx=ctx, S=S, us=round(us, 2))
 
 
+def bench_prompt_logprobs(ops):
+    """One full lm_head chunk (1,046 x 128,256 bf16, 268 MB: not cache resident): the
+    one-pass kernel at nreq 0 / 1 / 5 / 20 on all rows, the top_logprobs kernel on the same
+    buffer at n = 1 / 5 and a plain device copy, taken in alternation (one launch of each
+    per round, median over the rounds). TB/s is of the logits bytes (x2 for the copy)."""
+    R, V, K, rounds = 1046, 128256, 20, 12
+    logits = torch.empty(R, V, device=DEV, dtype=torch.bfloat16)
+    for a in range(0, R, 128):  # in slices: no fp32 copy of the whole buffer
+        logits[a:a + 128] = (torch.randn(min(128, R - a), V, device=DEV) * 3).to(torch.bfloat16)
+    dst = torch.empty_like(logits)
+    tg = torch.randint(0, V, (R,), device=DEV, dtype=torch.int32)
+    lp, rank = torch.empty(R, device=DEV), torch.empty(R, dtype=torch.int32, device=DEV)
+    ids, top = torch.empty(R, K, dtype=torch.int32, device=DEV), torch.empty(R, K, device=DEV)
+    nr = {n: torch.full((R,), n, dtype=torch.int32, device=DEV) for n in (0, 1, 5, 20)}
+    cases = [(f"prompt_logprobs n={n}", lambda n=n: ops.prompt_logprobs(logits, tg, nr[n], lp, rank, ids, top))
+             for n in (0, 1, 5, 20)]
+    cases += [(f"top_logprobs n={n}", lambda n=n: ops.top_logprobs(logits, nr[n], ids, top)) for n in (1, 5)]
+    cases += [("copy", lambda: dst.copy_(logits))]
+    for _, fn in cases:
+        fn()
+    torch.cuda.synchronize()
+    evs = {name: [] for name, _ in cases}
+    for _ in range(rounds):
+        for name, fn in cases:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            evs[name].append((a, b))
+    torch.cuda.synchronize()
+    nbytes = R * V * 2
+    for name, _ in cases:
+        ts = sorted(a.elapsed_time(b) * 1000 for a, b in evs[name])
+        us = ts[len(ts) // 2]
+        moved = nbytes * (2 if name == "copy" else 1)
+        emit(op=name, R=R, V=V, us=round(us, 1), min_us=round(ts[0], 1), max_us=round(ts[-1], 1),
+             logits_MB=round(nbytes / 1e6, 1), TBps=round(moved / us / 1e6, 3))
+
+
+def bench_prompt_logprobs_step(ops):
+    """Cost to a request: one prefill step of 8 x 1,024 tokens (llama-3-8b, dummy weights)
+    with and without prompt_logprobs=1, in alternation, and the lm_head + kernel part on its
+    own (the 8 x 1,023 scored rows through ModelRunner._prompt_logprobs)."""
+    import time
+
+    import numpy as np
+
+    from hipserve.config import EngineConfig
+    from hipserve.engine.llm_engine import LLMEngine
+    from hipserve.engine.model_runner import StepInputs
+    from hipserve.engine.request import SamplingParams
+
+    eng = LLMEngine(EngineConfig(model="llama-3-8b", load_format="dummy", max_num_seqs=64, max_num_batched_tokens=8192,
+                                 max_model_len=2048, num_kv_blocks=4096, enable_prefix_caching=False,
+                                 enforce_eager=True))
+    rng = np.random.default_rng(0)
+
+    def step(plp):
+        prompts = [rng.integers(10, 100000, 1024).tolist() for _ in range(8)]
+        for p in prompts:
+            eng.add_request(None, p, SamplingParams(temperature=0.0, max_tokens=1, ignore_eos=True, prompt_logprobs=plp))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = eng.step()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert len(outs) == 8 and not eng.has_unfinished()
+        return dt * 1e3
+
+    step(None), step(1)
+    ts = {None: [], 1: []}
+    for _ in range(5):
+        for plp in (None, 1):
+            ts[plp].append(step(plp))
+    base, scored = sorted(ts[None])[2], sorted(ts[1])[2]
+    r = eng.runner
+    m = 8 * 1023
+    hidden = torch.randn(8192, r.mcfg.hidden_size, device=DEV).to(torch.bfloat16)
+    inp = StepInputs(*([None] * 17))
+    inp.plp_rows = np.array([i for i in range(8192) if i % 1024 != 1023], np.int64)
+    inp.plp_targets = rng.integers(0, r.mcfg.vocab_size, m).astype(np.int32)
+    inp.plp_n = np.ones(m, np.int32)
+    part = timeit(lambda: r._prompt_logprobs(hidden, inp), n=5, warm=1) / 1e3
+    emit(op="prefill_step_8x1024", model="llama-3-8b", step_ms=round(base, 2), step_ms_prompt_logprobs_1=round(scored, 2),
+         step_ms_all=[round(t, 2) for t in ts[None]], step_ms_prompt_logprobs_1_all=[round(t, 2) for t in ts[1]],
+         diff_ms=round(scored - base, 2), lm_head_plus_kernel_ms=round(part, 2), scored_rows=m,
+         share_of_diff=round(part / max(scored - base, 1e-9), 3))
+
+
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     ops = KernelOps()
@@ -307,6 +398,10 @@ def main():
                      ("prefill_chunked", bench_prefill_chunked),
                      ("gemm", bench_gemm), ("norm", bench_norm), ("rope", bench_rope)]:
         if which in ("all", name):
+            fn(ops)
+    # by name only: a 268 MB buffer, and an 8B engine
+    for name, fn in [("prompt_logprobs", bench_prompt_logprobs), ("prompt_logprobs_step", bench_prompt_logprobs_step)]:
+        if which == name:
             fn(ops)
 
 
