@@ -335,3 +335,28 @@ void launch_vision_attention(void* out, void* qkv, const float* cos_sin, const i
 void launch_vision_pool_rmsnorm(void* out, const void* x, const void* w, int images, int g, int k, int C, float eps,
                                 hipStream_t s);
 }  // namespace hipserve
+
+namespace hipserve {
+// lora.hip — multi-LoRA: each row m of a batch uses the low-rank pair of adapter idx[m]
+// (int32, -1 or a value outside [0, slots): none). All tensors bf16 unless said otherwise.
+// shrink: t [M, R] = A[idx[m]] [R, K] @ x[m], fp32 over the whole of K, one rounding. K is cut
+// into `splits` slices (lora_shrink_splits; ws fp32 [splits, M, R] when > 1) that a second
+// stage sums in slice order. R % 16 == 0, <= 192; K % 64 == 0. Rows without an adapter get
+// zeros when splits > 1 and are left alone otherwise: the expand never reads them.
+int lora_shrink_splits(int M, int K);
+void launch_lora_shrink(void* t, float* ws, const void* x, long x_stride, const void* A, const int* idx, int M, int K,
+                        int R, int slots, int splits, hipStream_t s);
+// expand: out[m, n] += scale[idx[m]] * t[m, t_offset_j : t_offset_j + r] . B[idx[m], n, :] for
+// the slice j that holds column n (n_begin ascending from 0, multiples of 16); B [slots, N, r],
+// r 16 / 32 / 64, scale fp32 [slots]. out bf16 (added in fp32, rounded once) or fp32, row
+// stride out_stride; a row without an adapter is not written.
+constexpr int kLoraSlices = 3;
+struct LoraSlices {
+  int n;
+  int n_begin[kLoraSlices];
+  int t_offset[kLoraSlices];
+};
+void launch_lora_expand(void* out, bool out_f32, long out_stride, const void* t, int R, const void* B, int r,
+                        const float* scale, const int* idx, const LoraSlices& slices, int M, int N, int slots,
+                        hipStream_t s);
+}  // namespace hipserve

@@ -1326,6 +1326,52 @@ void moe_combine_add_rmsnorm(at::Tensor& out, at::Tensor& residual, const at::Te
                                            (float)eps, cur_stream());
 }
 
+// ---- multi-LoRA (lora.hip)
+// how many K slices a shrink of M rows takes (the caller sizes ws [splits, M, R] from it)
+int64_t lora_shrink_splits(int64_t M, int64_t K) { return hipserve::lora_shrink_splits((int)M, (int)K); }
+
+void lora_shrink(at::Tensor& t, const at::Tensor& x, const at::Tensor& A, const at::Tensor& idx, at::Tensor& ws,
+                 int64_t splits) {
+  Args a("lora_shrink", x, "x");
+  const void* xp = a.ptr(x, "x", BF16, ROWS8, {ANY, ANY});
+  const int64_t M = x.size(0), K = x.size(1);
+  const void* Ap = a.ptr(A, "A", BF16, CONTIG, {at_least(1), ANY, K});
+  const int64_t slots = A.size(0), R = A.size(1);
+  TORCH_CHECK(K % 64 == 0 && R % 16 == 0 && R >= 16 && R <= 192, "lora_shrink: K % 64 == 0, R a multiple of 16, <= 192");
+  TORCH_CHECK(M < (1 << 27) && slots * R * K < (1L << 40), "lora_shrink: too many rows");
+  TORCH_CHECK(splits >= 1 && splits <= 32, "lora_shrink: 1-32 splits");
+  void* tp = a.ptr(t, "t", BF16, CONTIG, {M, R});
+  const int* ip = a.as<int>(idx, "idx", CONTIG, exactly(M));
+  float* wsp = splits > 1 ? a.as<float>(ws, "ws", CONTIG, splits * M * R) : nullptr;
+  hipserve::launch_lora_shrink(tp, wsp, xp, x.stride(0), Ap, ip, M, K, R, slots, splits, cur_stream());
+}
+
+void lora_expand(at::Tensor& out, const at::Tensor& t, const at::Tensor& B, const at::Tensor& scale,
+                 const at::Tensor& idx, const std::vector<int64_t>& n_begin, const std::vector<int64_t>& t_offset) {
+  Args a("lora_expand", t, "t");
+  const void* tp = a.ptr(t, "t", BF16, CONTIG, {ANY, ANY});
+  const int64_t M = t.size(0), R = t.size(1);
+  const void* Bp = a.ptr(B, "B", BF16, CONTIG, {at_least(1), ANY, ANY});
+  const int64_t slots = B.size(0), N = B.size(1), r = B.size(2);
+  TORCH_CHECK(N % 16 == 0 && (r == 16 || r == 32 || r == 64), "lora_expand: N % 16 == 0, r one of 16, 32, 64");
+  unsigned which;
+  void* op = a.ptr(out, "out", BF16 | F32, ROWS4, {M, N}, &which);
+  const float* sp = a.as<float>(scale, "scale", CONTIG, exactly(slots));
+  const int* ip = a.as<int>(idx, "idx", CONTIG, exactly(M));
+  hipserve::LoraSlices sl;
+  sl.n = (int)n_begin.size();
+  TORCH_CHECK(sl.n >= 1 && sl.n <= hipserve::kLoraSlices && t_offset.size() == n_begin.size() && n_begin[0] == 0,
+              "lora_expand: 1-", hipserve::kLoraSlices, " slices (n_begin, t_offset), the first at column 0");
+  for (int j = 0; j < sl.n; ++j) {
+    TORCH_CHECK(n_begin[j] % 16 == 0 && n_begin[j] < N && (j == 0 || n_begin[j] > n_begin[j - 1]),
+                "lora_expand: slices begin at ascending multiples of 16 below N");
+    TORCH_CHECK(t_offset[j] >= 0 && t_offset[j] % 4 == 0 && t_offset[j] + r <= R, "lora_expand: a slice reads r columns of t");
+    sl.n_begin[j] = (int)n_begin[j];
+    sl.t_offset[j] = (int)t_offset[j];
+  }
+  hipserve::launch_lora_expand(op, which == F32, out.stride(0), tp, R, Bp, r, sp, ip, sl, M, N, slots, cur_stream());
+}
+
 // ---- vision tower (vision.hip)
 void layernorm(at::Tensor& out, const at::Tensor& x, const at::Tensor& w, const at::Tensor& b,
                const c10::optional<at::Tensor>& residual, double eps) {
@@ -1428,6 +1474,8 @@ void vision_pool_rmsnorm(at::Tensor& out, const at::Tensor& x, const at::Tensor&
   X(penalty_init, "(Tensor(a!) counts, Tensor(b!) seen, Tensor slots, Tensor off, Tensor n_prompt, Tensor toks) -> ()") \
   X(top_logprobs, "(Tensor logits, Tensor nreq, Tensor(a!) out_ids, Tensor(b!) out_lp) -> ()") \
   X(prompt_logprobs, "(Tensor logits, Tensor targets, Tensor nreq, Tensor(a!) out_lp, Tensor(b!) out_rank, Tensor(c!) out_ids, Tensor(d!) out_top) -> ()") \
+  X(lora_shrink, "(Tensor(a!) t, Tensor x, Tensor A, Tensor idx, Tensor(b!) ws, int splits) -> ()") \
+  X(lora_expand, "(Tensor(a!) out, Tensor t, Tensor B, Tensor scale, Tensor idx, int[] n_begin, int[] t_offset) -> ()") \
   X(layernorm, "(Tensor(a!) out, Tensor x, Tensor w, Tensor b, Tensor(b!)? residual, float eps) -> ()") \
   X(gelu_, "(Tensor(a!) x, bool tanh_approx) -> ()") \
   X(vision_pool_rmsnorm, "(Tensor(a!) out, Tensor x, Tensor w, int g, int k, float eps) -> ()") \
@@ -1448,6 +1496,7 @@ TORCH_LIBRARY(hipserve, m) {
   m.def("fp8_untile(Tensor(a!) out, Tensor q, int N, int K) -> ()", &fp8_untile);
   m.def("quant_formats() -> str", &quant_formats);
   m.def("qmoe_gemm(Tensor(a!) out, Tensor(b!) ws, Tensor x, Tensor q, Tensor rs, int qtype, int N, int K, Tensor slots, Tensor tile_expert, int tile, int gather_k, int splits, bool kmajor=False, int glu=0) -> int", &qmoe_gemm);
+  m.def("lora_shrink_splits(int M, int K) -> int", &lora_shrink_splits);
   m.def("stage_copy(Tensor(a!)[] dst, Tensor[] src, int device) -> ()", &stage_copy);
   m.def("car_create(int rank, int world, int max_bytes, int nb_large=512) -> int", &car_create);
   m.def("car_handle(int state) -> Tensor", &car_handle);

@@ -661,6 +661,12 @@ class EngineConfig:
     # scales: half the KV bytes per token, so 2x the KV blocks and half the decode
     # attention's HBM stream; K / V are rounded to e4m3 when written)
     kv_cache_dtype: str = "auto"
+    # multi-LoRA (hipserve/lora.py): PEFT adapters {name: directory}, all resident; a request
+    # selects one by its `model` name
+    enable_lora: bool = False
+    lora_modules: dict = field(default_factory=dict)
+    max_loras: int | None = None         # slots; default: the number of adapters listed
+    max_lora_rank: int = 16              # 8, 16, 32 or 64
     host: str = "0.0.0.0"
     port: int = 8080
     extra: dict = field(default_factory=dict)
@@ -672,6 +678,10 @@ class EngineConfig:
             raise ValueError(f"block_size must be a power of two in [16, 256], got {b}")
         if self.kv_cache_dtype not in KV_CACHE_DTYPES:
             raise ValueError(f"kv_cache_dtype must be one of {sorted(KV_CACHE_DTYPES)}, got {self.kv_cache_dtype!r}")
+        if self.lora_modules and not self.enable_lora:
+            raise ValueError("--lora-modules needs --enable-lora")
+        if self.served_model_name in self.lora_modules or self.model in self.lora_modules:
+            raise ValueError("a LoRA adapter cannot take the base model's name")
 
     @property
     def kv_fp8(self) -> bool:

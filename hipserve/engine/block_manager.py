@@ -7,8 +7,17 @@ from .request import Sequence
 
 def _hash_prompt(seq: Sequence) -> list[int]:
     """Prompt ids as prefix-cache keys: image placeholder tokens are keyed by their
-    image's content (two prompts with different images never share KV blocks)."""
-    return seq.mm.hash_ids if seq.mm is not None else seq.prompt_token_ids
+    image's content (two prompts with different images never share KV blocks), and the
+    first id by the sequence's LoRA adapter: the block hashes are chained, so sequences under
+    different adapters (or the base model) share no block as long as their first keys differ.
+    The adapter key is a negative int32 like the image content ids, so that rests on no
+    prompt starting with an image token whose content id equals another prompt's adapter key
+    (prompts start with BOS or text)."""
+    ids = seq.mm.hash_ids if seq.mm is not None else seq.prompt_token_ids
+    if seq.lora_slot < 0:
+        return ids
+    # the pool's keys are int32: slot + 1 above 20 bits of the id (vocabularies are below 2^20)
+    return [-((((seq.lora_slot + 1) & 0x3FF) << 20) + (ids[0] & 0xFFFFF))] + ids[1:]
 
 
 class BlockManager:

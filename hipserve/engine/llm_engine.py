@@ -6,6 +6,7 @@ tokens -> stop checks (EOS / stop ids / stop strings / max_tokens / max_model_le
 """
 from __future__ import annotations
 
+import dataclasses
 import itertools
 import random
 import time
@@ -69,6 +70,7 @@ class LLMEngine:
                                  "one image: image tokens attend to each other across the whole image")
         self.runner = ModelRunner(cfg, self.model_cfg, self.tp)
         self.max_model_len = self.runner.max_model_len
+        self.lora_names = list(self.runner.lora.names) if self.runner.lora is not None else []
         self.blocks = BlockManager(self.runner.usable_blocks, cfg.block_size, cfg.enable_prefix_caching)
         self.scheduler = Scheduler(self.blocks, cfg.max_num_seqs, cfg.max_num_batched_tokens,
                                    self.max_model_len)
@@ -110,6 +112,10 @@ class LLMEngine:
         if len(ids) >= self.max_model_len:
             raise ValueError(f"prompt has {len(ids)} tokens; max_model_len is {self.max_model_len}")
         seq = Sequence(request_id, ids, params, eos_token_ids=self.eos_ids)
+        if params.lora is not None:
+            if params.lora not in self.lora_names:
+                raise ValueError(f"unknown LoRA adapter {params.lora!r}; resident: {self.lora_names}")
+            seq.lora_slot = self.lora_names.index(params.lora)
         vcfg = self.model_cfg.vision
         if images and params.prompt_logprobs is not None:
             # placeholder rows stand for image features: no token is their meaningful target
@@ -347,10 +353,14 @@ class LLMEngine:
                              seq.num_prompt_tokens, len(seq.output_token_ids), None, seq.output_text)
 
     # ---------------------------------------------------------------- offline
-    def generate(self, prompts, params: SamplingParams | list[SamplingParams]):
-        """Blocking batch generation; returns {request_id: (token_ids, text, reason)}."""
+    def generate(self, prompts, params: SamplingParams | list[SamplingParams], lora=None):
+        """Blocking batch generation; returns {request_id: (token_ids, text, reason)}.
+        ``lora``: a resident adapter's name for all prompts, or one name / None per prompt."""
         if not isinstance(params, list):
             params = [params] * len(prompts)
+        if lora is not None:
+            names = lora if isinstance(lora, (list, tuple)) else [lora] * len(prompts)
+            params = [dataclasses.replace(sp, lora=n) for sp, n in zip(params, names)]
         order = []
         for p, sp in zip(prompts, params):
             order.append(self.add_request(None, p, sp).request_id)

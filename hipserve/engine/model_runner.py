@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from ..config import EngineConfig, ModelConfig
+from ..lora import LoraBatch, LoraSet
 from ..models.llama import AttnMeta, LlamaModel
 from ..ops import get_ops
 from ..parallel.comm import TPGroup
@@ -76,6 +77,9 @@ class StepInputs:
     plp_rows: np.ndarray | None = None    # int64 [m]: rows of the batch
     plp_targets: np.ndarray | None = None  # int32 [m]: the prompt token that follows each row
     plp_n: np.ndarray | None = None       # int32 [m]: alternatives wanted per row (0: none)
+    # multi-LoRA: the adapter slot of every row of ids (one entry per prefill token; -1: base
+    # model, padding rows too); None on a step with no adapter row
+    lora_idx: np.ndarray | None = None
 
 
 def prompt_logprob_span(ss) -> tuple[int, int]:
@@ -142,6 +146,15 @@ class ModelRunner:
             self.model.fused_qkv_attention = False
         t0 = time.time()
         self._load_weights()
+        self.lora = None
+        if ecfg.enable_lora:  # all listed adapters resident, refused by name here if not servable
+            if str(ecfg.extra.get("single_layout", "auto")) == "1":
+                raise ValueError("--enable-lora cannot run with a forced single layout (single_layout=1)")
+            self.lora = LoraSet(self.model, ecfg.lora_modules, ecfg.max_loras, ecfg.max_lora_rank)
+            log.info("LoRA: %d adapter(s) %s in %d slot(s), %.1f MiB, on %s; row-major gate|up weights are kept "
+                     "(the single packed layout is not chosen)",
+                     len(self.lora.names), self.lora.names, self.lora.num_slots, self.lora.bytes() / 2**20,
+                     ", ".join(self.lora.targets))
         self.load_time = time.time() - t0
         from ..utils.faults import FaultInjector
 
@@ -318,6 +331,8 @@ class ModelRunner:
         times at least as fast as hipBLASLt on this model's prefill units."""
         mode = os.environ.get("HIPSERVE_SINGLE_LAYOUT", self.ecfg.extra.get("single_layout", "auto"))
         m = self.model
+        if self.ecfg.enable_lora:  # adapters add to gate|up before the activation: row-major weights stay
+            return None            # (a forced single layout was refused when the adapters were loaded)
         if str(mode) == "0" or not hasattr(m, "single_layout_ok") or not m.single_layout_ok():
             return None
         if str(mode) == "1":
@@ -571,6 +586,10 @@ class ModelRunner:
                          np.array(rows, dtype=np.int64), temp, topk, topp, seeds, steps,
                          pen_slot, pen_vals, nlp, pen_init, topn,
                          min_p=minp, bias_slot=bias_slot, bias_init=bias_init)
+        if any(s.seq.lora_slot >= 0 for s in seqs):
+            li = np.full(len(ids), -1, np.int32)
+            li[:sum(s.num_tokens for s in seqs)] = np.repeat([s.seq.lora_slot for s in seqs], [s.num_tokens for s in seqs])
+            inp.lora_idx = li
         if plp_rows:
             inp.plp_rows = np.array(plp_rows, np.int64)
             inp.plp_targets = np.array(plp_tg, np.int32)
@@ -690,6 +709,8 @@ class ModelRunner:
             meta.tmp_ml = torch.empty(inp.num_decode, *self.tmp_ml.shape[1:], device=self.device)
         if "mm" in inp.extra:
             self._attach_mm(inp.extra["mm"], meta, len(inp.ids))
+        if inp.lora_idx is not None:
+            meta.lora = LoraBatch(self._t(inp.lora_idx), self.lora)
         hidden = self.model.forward(ids, meta, self.kv)
         if inp.plp_rows is not None:
             inp.extra["prompt_logprobs"] = self._prompt_logprobs(hidden, inp)
@@ -801,12 +822,14 @@ class ModelRunner:
         meta.mm_deepstack = [torch.cat([d[j] for d in dss]).to(self.model.dtype) for j in range(len(dss[0]))]
 
     # ------------------------------------------------------------ hipGraphs
-    def _graph_forward(self, b: int, full: bool = True):
+    def _graph_forward(self, b: int, full: bool = True, lora: bool = False):
         """The captured decode step. The lean variant (``full=False``) leaves out the
         OpenAI logit_bias, penalty and top-n logprob kernels and the sampler's second
         threshold round (needed only by rows that combine top-k with top-p); a step
         whose rows need none of them replays it: six launches fewer, ~35 us of a
-        ~5.4 ms Llama-3-8B step. min_p is a per-row input of the sampler in both."""
+        ~5.4 ms Llama-3-8B step. min_p is a per-row input of the sampler in both.
+        ``lora``: the variant of a LoRA engine whose rows take their adapters from the staged
+        ``aslot`` region; a step without an adapter row replays the plain variant."""
         st = self._static
         meta = AttnMeta(num_prefill_tokens=0, num_decode=b, positions=st["pos"][:b],
                         slot_mapping=st["slots"][:b], bt_decode=st["bt"][:b], ctx_decode=st["ctx"][:b],
@@ -814,6 +837,8 @@ class ModelRunner:
         # lookahead ids: resolved inside the model's first kernel when it can
         # (embed_rmsnorm), else by the model's id select (LlamaModel.resolve_ids)
         meta.id_src = (st["src"][:b], st["tok"])
+        if lora:
+            meta.lora = LoraBatch(st["aslot"][:b], self.lora)
         hidden = self.model.forward(st["ids"][:b], meta, self.kv)
         logits = self.model.compute_logits(hidden)
         # penalties / top-n logprobs: early-exit kernels for rows that want none; top-n
@@ -845,13 +870,15 @@ class ModelRunner:
     @torch.inference_mode()
     def _capture_graphs(self):
         mb, W, dev = self.buckets[-1], self.width, self.device
+        n32 = 5 if self.lora is None else 6  # int32 regions of mb rows after the block tables (LoRA: + aslot)
+        variants = (False,) if self.lora is None else (False, True)
         # host staging (pinned, double-buffered by launch parity so step k+1 can be
         # staged while step k runs) and device static buffers, one region per dtype
         self._stage = []
         for _ in range(2):
             self._stage.append({
                 "h64": torch.zeros(6 * mb, dtype=torch.long).pin_memory(),
-                "h32": torch.zeros(mb * W + 5 * mb, dtype=torch.int32).pin_memory(),
+                "h32": torch.zeros(mb * W + n32 * mb, dtype=torch.int32).pin_memory(),
                 "hf": torch.zeros(6 * mb, dtype=torch.float32).pin_memory(),
                 "tok": torch.zeros(mb, dtype=torch.long).pin_memory(),
                 "lp": torch.zeros(mb, dtype=torch.float32).pin_memory(),
@@ -860,12 +887,12 @@ class ModelRunner:
                 "done": None,
                 "bias_set": False, "minp_set": False,   # the set holds non-default bias slots / min_p
             })
-            self._stage[-1]["h32"][mb * W + 4 * mb:].fill_(-1)   # logit_bias slots: none
+            self._stage[-1]["h32"][mb * W + 4 * mb:].fill_(-1)   # logit_bias slots (and adapter slots): none
         self._launches = 0
         # HIPSERVE_STAGE_COPY=blit: per-buffer hipMemcpyAsync instead of the staging kernel
         self._stage_kernel = os.environ.get("HIPSERVE_STAGE_COPY", "kernel") != "blit"
         d64 = torch.zeros(6 * mb, dtype=torch.long, device=dev)
-        d32 = torch.zeros(mb * W + 5 * mb, dtype=torch.int32, device=dev)
+        d32 = torch.zeros(mb * W + n32 * mb, dtype=torch.int32, device=dev)
         df = torch.zeros(6 * mb, dtype=torch.float32, device=dev)
         st = {
             "d64": d64, "d32": d32, "df": df,
@@ -875,6 +902,7 @@ class ModelRunner:
             "topk": d32[mb * W + mb: mb * W + 2 * mb],
             "pslot": d32[mb * W + 2 * mb: mb * W + 3 * mb], "nlp": d32[mb * W + 3 * mb: mb * W + 4 * mb],
             "bslot": d32[mb * W + 4 * mb: mb * W + 5 * mb],
+            "aslot": d32[mb * W + 5 * mb:],  # LoRA engines: the rows' adapter slots (-1: base); else empty
             "temp": df[0:mb], "topp": df[mb:2 * mb],
             "pres": df[2 * mb:3 * mb], "freq": df[3 * mb:4 * mb], "rep": df[4 * mb:5 * mb],
             "minp": df[5 * mb:6 * mb],
@@ -891,6 +919,7 @@ class ModelRunner:
         st["src"].fill_(-1)
         st["pslot"].fill_(-1)
         st["bslot"].fill_(-1)
+        st["aslot"].fill_(-1)
         st["rep"].fill_(1.0)
         t0 = time.time()
         # TP ranks enter the captured collectives together (the tuner and the
@@ -910,7 +939,8 @@ class ModelRunner:
             self._graph_forward(self.buckets[-1])
             for b in reversed(self.buckets):
                 for full in (True, False):
-                    self._graph_forward(b, full)
+                    for lora in variants:
+                        self._graph_forward(b, full, lora)
         stream.synchronize()
         torch.cuda.synchronize(dev)
         self.tp.barrier()
@@ -920,15 +950,15 @@ class ModelRunner:
             # copies captured inside, so consecutive steps are back-to-back graphs
             # (a standalone dispatch after a graph waits ~0.2 ms for the graph's end)
             for par in ((0, 1) if self._stage_kernel else (None,)):
-                for full in (True, False):
+                for full, lora in ((f, v) for f in (True, False) for v in variants):
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, pool=self.graph_pool, stream=stream):
                         if par is not None:
                             self._stage_in(b, self._stage[par])
-                        self._graph_forward(b, full)
+                        self._graph_forward(b, full, lora)
                         if par is not None:
                             self._stage_out(b, self._stage[par])
-                    self.graphs[(b, par, full)] = g
+                    self.graphs[(b, par, full) + (("lora",) if lora else ())] = g
         torch.cuda.synchronize(dev)
         self.graph_capture_time = time.time() - t0
 
@@ -980,6 +1010,11 @@ class ModelRunner:
             sg["bias_set"] = inp.bias_slot is not None
             if sg["bias_set"]:
                 a32[o + 2 * mb:o + 2 * mb + n] = inp.bias_slot
+        if self.lora is not None:  # adapter slots; padding rows take none
+            a32[o + 3 * mb:o + 3 * mb + b] = -1
+            if inp.lora_idx is not None:
+                a32[o + 3 * mb:o + 3 * mb + n] = inp.lora_idx[:n]
+        var = ("lora",) if inp.lora_idx is not None else ()
         af = hf.numpy()
         af[0:n] = inp.temperature
         af[n:b] = 0.0
@@ -1001,13 +1036,13 @@ class ModelRunner:
         full = (inp.pen_slot is not None or inp.nlogprobs is not None or inp.bias_slot is not None
                 or bool(np.any((inp.top_k[:n] > 0) & (inp.top_p[:n] < 1.0))))
         if self._stage_kernel:  # the graph of this parity stages in/out itself
-            self.graphs[(b, (self._launches - 1) & 1, full)].replay()
+            self.graphs[(b, (self._launches - 1) & 1, full) + var].replay()
         else:
             st["d64"].copy_(h64, non_blocking=True)
             st["d32"][: b * W].copy_(h32[: b * W], non_blocking=True)
             st["d32"][mb * W:].copy_(h32[mb * W:], non_blocking=True)
             st["df"].copy_(hf, non_blocking=True)
-            self.graphs[(b, None, full)].replay()
+            self.graphs[(b, None, full) + var].replay()
             for k in ("tok", "lp", "top_ids", "top_lp"):
                 sg[k][:n].copy_(st[k][:n], non_blocking=True)
         ev = torch.cuda.Event()

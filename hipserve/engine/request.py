@@ -86,6 +86,7 @@ class SamplingParams:
     logit_bias: object = None   # {token id: bias}; normalised to a sorted list of (id, bias)
     # log-prob and rank of every prompt token plus this many alternatives (vLLM's field; 0: none)
     prompt_logprobs: int | None = None
+    lora: str | None = None     # name of a resident LoRA adapter (the API sets it from `model`); None: base
 
     def __post_init__(self):
         """Coerce and range-check every field: a value that reaches the engine
@@ -168,6 +169,7 @@ class Sequence:
     pen_slot: int | None = None         # device penalty-state slot (ModelRunner), while it has penalties
     bias_slot: int | None = None        # device logit_bias slot (ModelRunner), while it has a bias
     mm: object = None                   # multimodal.MMState of a prompt with images
+    lora_slot: int = -1                 # slot of its LoRA adapter (hipserve/lora.py); -1: the base model
     # params.prompt_logprobs: one (logprob, rank, [(id, logprob), ...]) per prompt position >= 1,
     # in order; its length is the number of positions scored so far (kept across a preemption)
     prompt_logprobs: list = field(default_factory=list)

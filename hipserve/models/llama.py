@@ -67,6 +67,9 @@ class AttnMeta:
     # decode lookahead (model_runner): (src, tok) — row i's input id is tok[src[i]]
     # where src[i] >= 0 (the previous graph step's sampled id), else ids[i]
     id_src: tuple | None = None
+    # multi-LoRA (hipserve/lora.py LoraBatch): the rows' adapter slots and the slot tensors;
+    # None: every code path is the base model's
+    lora: object = None
 
 
 @dataclass
@@ -643,7 +646,7 @@ class LlamaModel(MoEMixin):
             self.ops.fused_add_rmsnorm(out, x, residual, w, eps, out8=out8p)
         return out
 
-    def post_add_rmsnorm(self, out, residual, pt, x, w, w_post, w_next, out16=None, out8=None):
+    def post_add_rmsnorm(self, out, residual, pt, x, w, w_post, w_next, out16=None, out8=None, h=None):
         """Sandwich-norm epilogue (Gemma-3): residual += RMSNorm(sum over the TP ranks
         of x @ w.T) * w_post; out = RMSNorm(residual) * w_next. At TP = 1 one kernel
         over the split-K partials ``pt`` when the decode GEMM wrote them (also writing
@@ -663,8 +666,8 @@ class LlamaModel(MoEMixin):
         elif pt is not None:
             o = torch.empty_like(residual)
             torch.ops.hipserve.splitk_reduce(o, pt[0], pt[1])
-        else:
-            o = self.linear_rowpar(x, w)
+        else:  # h: the projection where the caller already has it (with its LoRA delta)
+            o = self.linear_rowpar(x, w) if h is None else h
         if not tp1:
             o = self._tp_sum(o, residual)
         self.ops.rmsnorm(o, o, w_post, eps)
@@ -748,6 +751,7 @@ class LlamaModel(MoEMixin):
         x8 = self._x8p(xn, self.layers[0].wqkv)  # FP8 models: the norm writes the e4m3 GEMM input too
         ops.rmsnorm(xn, h, self.layers[0].ln1, eps, out8=x8)
         L = len(self.layers)
+        lo = meta.lora  # adapters add to a projection's plain output: no GEMM-epilogue shortcut below
         for i, lw in enumerate(self.layers):
             # prefill-sized batches: FP8 W8A8 (ops/pgemm.py), the packed-layout GEMM of a
             # single-layout model (gemm.linear dispatches PackedLinear), else hipBLASLt
@@ -757,6 +761,8 @@ class LlamaModel(MoEMixin):
                 qkv = self.linear(xn, lw.wqkv)
             if lw.bqkv is not None:
                 qkv += lw.bqkv
+            if lo is not None:
+                lo.apply(ops, i, "qkv", xn, qkv)
             if lw.q_norm is not None:  # per-head RMSNorm of q and k, before RoPE
                 ops.qk_rmsnorm(qkv, lw.q_norm, lw.k_norm, nq, nkv, D, eps)
             kc, vc = kv_caches[i]
@@ -771,7 +777,8 @@ class LlamaModel(MoEMixin):
                 ops.paged_decode(attn[Tp:Tp + Td], qkv[Tp:Tp + Td], kc, vc, meta.bt_decode, meta.ctx_decode,
                                  tmp_out, tmp_ml, nq, nkv, part, self.scale, win, None, cfg.attn_softcap)
             x8 = self._x8p(xn, lw.wgu, glu=True)
-            self._rowpar_norm(xn, residual, attn, lw.wo, lw.post_attn_norm, lw.ln2, x8)
+            ho = lo.apply(ops, i, "o", attn, self.linear_rowpar(attn, lw.wo)) if lo is not None and lo.has(i, "o") else None
+            self._rowpar_norm(xn, residual, attn, lw.wo, lw.post_attn_norm, lw.ln2, x8, ho)
             nxt = self.layers[i + 1].ln1 if i + 1 < L else self.norm
             x8n = self._x8p(xn, self.layers[i + 1].wqkv) if i + 1 < L else None  # next layer's qkv input
             act = h = None  # the down projection's input, or its output where already computed
@@ -779,7 +786,11 @@ class LlamaModel(MoEMixin):
                 h = self.moe(xn, lw)
             else:
                 gelu = cfg.hidden_act == "gelu_tanh"
-                if pgemm.f8_use(lw.wgu, T, glu=True):  # FP8 gate|up
+                if lo is not None and lo.has(i, "gu"):  # the GLU-in-epilogue forms have no pre-activation output
+                    gu = lo.apply(ops, i, "gu", xn, self.linear(xn, lw.wgu))
+                    act = torch.empty(T, self.inter, device=xn.device, dtype=xn.dtype)
+                    self.act_and_mul(act, gu)
+                elif pgemm.f8_use(lw.wgu, T, glu=True):  # FP8 gate|up
                     act8 = None
                     if pgemm.f8_use(lw.wd, T):  # FP8 down too: act straight to e4m3 (glu_quant)
                         act8 = pgemm.f8_glu_q8(xn, lw.wgu, gelu, x8)
@@ -795,6 +806,8 @@ class LlamaModel(MoEMixin):
                     gu = self.linear(xn, lw.wgu)
                     act = torch.empty(T, self.inter, device=xn.device, dtype=xn.dtype)
                     self.act_and_mul(act, gu)
+                if lo is not None and lo.has(i, "d") and h is None:
+                    h = lo.apply(ops, i, "d", act, self.linear_rowpar(act, lw.wd))
             # DeepStack (Qwen3-VL): visual features join the residual stream after layers 0..n-1
             add = (meta.mm_rows, ds[i]) if ds is not None and i < len(ds) else None
             self._rowpar_norm(xn, residual, act, lw.wd, lw.post_ff_norm, nxt, x8n, h, add)
@@ -845,6 +858,9 @@ class LlamaModel(MoEMixin):
         # 32K x 4: 232 vs 239; profiles/r6_qkv_attn_long_ab.log)
         one_part = -(-meta.bt_decode.shape[1] * self.block_size_hint // part) == 1
         L = len(self.layers)
+        # adapters: where a projection leaves split-K partials, the expand adds its fp32 delta to
+        # partial slice 0 ahead of the consuming epilogue; elsewhere to the bf16 output
+        lo = meta.lora
         for i, lw in enumerate(self.layers):
             kc, vc = kv_caches[i]
             win = cfg.window_of(i)
@@ -853,6 +869,8 @@ class LlamaModel(MoEMixin):
             fuse_qa = one_part and self.fused_qkv_attn_ok(i) and kc.element_size() == 2
             cs = self.cos_sin_local if win else self.cos_sin
             pt = self._partial(xn, lw.wqkv, xn16, xn8)
+            if lo is not None and pt is not None:
+                lo.apply_partial(ops, i, "qkv", xn, pt)
             attn16 = self._x16(attn, lw.wo)  # the attention's f16 pair-order copy for a quantised o_proj
             if pt is not None and fuse_qa:
                 # RoPE + KV write + attention in one kernel, straight from the partials
@@ -868,6 +886,8 @@ class LlamaModel(MoEMixin):
                 qkv = self.linear(xn, lw.wqkv)
                 if lw.bqkv is not None:
                     qkv += lw.bqkv
+                if lo is not None:
+                    lo.apply(ops, i, "qkv", xn, qkv)
                 if lw.q_norm is not None:
                     ops.qk_rmsnorm(qkv, lw.q_norm, lw.k_norm, nq, nkv, D, eps)
                 ops.rope_cache(qkv, meta.positions, meta.slot_mapping, cs, kc, vc, nq, nkv, D,
@@ -875,7 +895,8 @@ class LlamaModel(MoEMixin):
             if pt is None or not fuse_qa:
                 ops.paged_decode(attn, qkv, kc, vc, meta.bt_decode, meta.ctx_decode, tmp_out, tmp_ml,
                                  nq, nkv, part, self.scale, win, attn16, cfg.attn_softcap)
-            xn16, xn8 = self._decode_rowpar_norm(xn, residual, attn, lw.wo, attn16, lw.post_attn_norm, lw.ln2, lw.wgu)
+            xn16, xn8 = self._decode_rowpar_norm(xn, residual, attn, lw.wo, attn16, lw.post_attn_norm, lw.ln2, lw.wgu,
+                                                 (lo, i, "o"))
             nxt = self.layers[i + 1].ln1 if i + 1 < L else self.norm
             if lw.router is not None:  # MoE MLP: routed expert GEMMs, then residual + next norm
                 # TP = 1: the expert combine adds the residual and runs the next norm itself
@@ -887,10 +908,13 @@ class LlamaModel(MoEMixin):
                     self.add_rmsnorm(xn, residual, y, 1, nxt)
                 continue
             gelu = cfg.hidden_act == "gelu_tanh"
-            gc = None if gelu else gemm.glu_choice(T, lw.wgu)
+            lgu = lo is not None and lo.has(i, "gu")  # no GLU-in-epilogue form: it has no pre-activation output
+            gc = None if gelu or lgu else gemm.glu_choice(T, lw.wgu)
             pt = (None if gc is not None or (isinstance(lw.wgu, torch.Tensor) and not gelu)
                   else self._partial(xn, lw.wgu, xn16, xn8))
             act16 = None
+            if lgu and pt is not None:
+                lo.apply_partial(ops, i, "gu", xn, pt)
             if gc is not None:    # SiLU-GLU in the gate|up GEMM's epilogue
                 act = gemm.gemm_glu(xn, lw.wgu, gc)
             elif pt is not None:   # quantised gate|up, or GeGLU: the GLU over the plain-layout partials
@@ -903,13 +927,16 @@ class LlamaModel(MoEMixin):
                 act = gemm.packed_glu(xn, lw.wgu, gelu)
             else:
                 gu = self.linear(xn, lw.wgu)
+                if lgu:
+                    lo.apply(ops, i, "gu", xn, gu)
                 act = torch.empty(T, self.inter, device=xn.device, dtype=xn.dtype)
                 self.act_and_mul(act, gu)
             consumer = self.layers[i + 1].wqkv if i + 1 < L else None
-            xn16, xn8 = self._decode_rowpar_norm(xn, residual, act, lw.wd, act16, lw.post_ff_norm, nxt, consumer)
+            xn16, xn8 = self._decode_rowpar_norm(xn, residual, act, lw.wd, act16, lw.post_ff_norm, nxt, consumer,
+                                                 (lo, i, "d"))
         return xn
 
-    def _decode_rowpar_norm(self, xn, residual, x, w, x16, post_w, next_w, consumer):
+    def _decode_rowpar_norm(self, xn, residual, x, w, x16, post_w, next_w, consumer, lora=(None, 0, "")):
         """The fused decode layer's o_proj / down_proj tail: as ``_rowpar_norm``, over the
         decode GEMM's split-K partials where the tuner picked it (``x16``: see ``_partial``),
         else the unfused projection. Returns the (f16, e4m3) copies of xn the epilogue also
@@ -917,13 +944,20 @@ class LlamaModel(MoEMixin):
         pt = self._partial(x, w, x16)
         xn16 = self._x16(xn, consumer) if pt is not None else None
         xn8 = self._x8(xn, consumer) if pt is not None else None
+        lo, layer, proj = lora
+        h = None  # the unfused projection with its adapter delta (``lora``: the step's LoraBatch, layer, "o" / "d")
+        if lo is not None and lo.has(layer, proj):
+            if pt is not None:
+                lo.apply_partial(self.ops, layer, proj, x, pt)
+            else:
+                h = lo.apply(self.ops, layer, proj, x, self.linear_rowpar(x, w))
         if post_w is not None:  # Gemma sandwich norm
-            if not self.post_add_rmsnorm(xn, residual, pt, x, w, post_w, next_w, xn16, xn8):
+            if not self.post_add_rmsnorm(xn, residual, pt, x, w, post_w, next_w, xn16, xn8, h):
                 xn16 = xn8 = None
         elif pt is not None:
             self.add_rmsnorm(xn, residual, pt[0], pt[1], next_w, xn16, xn8)
         else:
-            self.add_rmsnorm(xn, residual, self.linear_rowpar(x, w), 1, next_w)
+            self.add_rmsnorm(xn, residual, self.linear_rowpar(x, w) if h is None else h, 1, next_w)
         return xn16, xn8
 
     def quant_weights(self) -> list:

@@ -166,6 +166,21 @@ class KernelOps:
         self._op.vision_pool_rmsnorm(out, x, w, g, k, eps)
         return out
 
+    # ---- multi-LoRA (csrc/kernels/lora.hip)
+    LORA_WS_ROWS = 4096  # rows of fp32 [*, R] split-K partials a shrink needs at most (splits * M when split)
+
+    def lora_shrink(self, t, x, A, idx, ws):
+        """t [M, R] = A[idx[m]] @ x[m]; ws: fp32 workspace of LORA_WS_ROWS * R elements."""
+        M, K = x.shape
+        splits = self._op.lora_shrink_splits(M, K)
+        self._op.lora_shrink(t, x, A, idx, ws, splits)
+        return t
+
+    def lora_expand(self, out, t, B, scale, idx, slices):
+        """out [M, N] (bf16, or fp32 split-K slice 0) += scale * t . B per row; slices: (n_begin, t_offset) pairs."""
+        self._op.lora_expand(out, t, B, scale, idx, [s[0] for s in slices], [s[1] for s in slices])
+        return out
+
 
 class ReferenceOps:
     """PyTorch reference path (CPU plumbing engine / numerics oracle)."""
@@ -261,6 +276,12 @@ class ReferenceOps:
     def vision_pool_rmsnorm(self, out, x, w, g, k, eps):
         out.copy_(ref.vision_pool_rmsnorm(x, w, g, k, eps))
         return out
+
+    def lora_shrink(self, t, x, A, idx, ws=None):
+        return ref.lora_shrink(t, x, A, idx)
+
+    def lora_expand(self, out, t, B, scale, idx, slices):
+        return ref.lora_expand(out, t, B, scale, idx, slices)
 
     def sample(self, out_tok, out_lp, logits, temperature, top_k, top_p, seeds, steps, two_rounds=True,
                min_p=None):

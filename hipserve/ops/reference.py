@@ -473,3 +473,34 @@ def prompt_logprobs(logits, targets, nreq, out_lp, out_rank, out_ids, out_top):
         lt = l[t]
         out_lp[r] = float("-inf") if lt == float("-inf") else lt - torch.logsumexp(l, 0)
         out_rank[r] = 1 + int((l > lt).sum()) + int((l[:t] == lt).sum())
+
+
+def lora_shrink(t, x, A, idx):
+    """t[m] = A[idx[m]] @ x[m] per batch row (csrc/kernels/lora.hip): fp32 over the whole of K
+    (the tensors' own type where that is wider), one rounding to t's type; rows with
+    idx < 0 get zeros."""
+    acc = torch.promote_types(x.dtype, torch.float32)
+    t.zero_()
+    for a in torch.unique(idx).tolist():
+        if a < 0:
+            continue
+        rows = (idx == a).nonzero().flatten()
+        t[rows] = (x[rows].to(acc) @ A[a].to(acc).t()).to(t.dtype)
+    return t
+
+
+def lora_expand(out, t, B, scale, idx, slices):
+    """out[m, n] += scale[idx[m]] * t[m, off_j : off_j + r] . B[idx[m], n, :] for the slice
+    j = (n_begin, t_offset) holding column n; summed and scaled in fp32, added to out in
+    fp32 and rounded once. Rows with idx < 0 are not written."""
+    N, r = B.shape[1], B.shape[2]
+    acc = torch.promote_types(t.dtype, torch.float32)
+    ends = [s[0] for s in slices[1:]] + [N]
+    for a in torch.unique(idx).tolist():
+        if a < 0:
+            continue
+        rows = (idx == a).nonzero().flatten()
+        for (n0, off), n1 in zip(slices, ends):
+            d = t[rows, off:off + r].to(acc) @ B[a, n0:n1].to(acc).t() * scale[a].to(acc)
+            out[rows, n0:n1] = (out[rows, n0:n1].to(acc) + d).to(out.dtype)
+    return out

@@ -54,11 +54,12 @@ def _has_images(msgs) -> bool:
 
 class OpenAIServer:
     def __init__(self, aengine: AsyncEngine, model_name: str, max_model_len: int,
-                 extra_names: tuple = ()):
+                 extra_names: tuple = (), lora_names: tuple = ()):
         self.ae = aengine
         self.engine = aengine.engine
         self.model_name = model_name
         self.names = {model_name, *extra_names}
+        self.lora_names = set(lora_names)  # resident adapters: `model: <name>` selects one
         self.max_model_len = max_model_len
         self.created = int(time.time())
         self.tokenizer = self.engine.tokenizer
@@ -94,6 +95,9 @@ class OpenAIServer:
         data = [{"id": n, "object": "model", "created": self.created, "owned_by": "hipserve",
                  "root": self.engine.cfg.model, "max_model_len": self.max_model_len}
                 for n in sorted(self.names)]
+        data += [{"id": n, "object": "model", "created": self.created, "owned_by": "hipserve",
+                  "root": self.engine.cfg.lora_modules.get(n, n), "parent": self.model_name,
+                  "max_model_len": self.max_model_len} for n in sorted(self.lora_names)]
         return web.json_response({"object": "list", "data": data})
 
     async def metrics(self, request):
@@ -115,7 +119,7 @@ class OpenAIServer:
     # ------------------------------------------------------------ helpers
     def _check_model(self, body):
         m = body.get("model")
-        if m is not None and m not in self.names:
+        if m is not None and m not in self.names and m not in self.lora_names:
             return _err(404, f"The model `{m}` does not exist.", "NotFoundError", 404)
         return None
 
@@ -150,7 +154,8 @@ class OpenAIServer:
             seed=body.get("seed"), presence_penalty=opt("presence_penalty", 0.0),
             frequency_penalty=opt("frequency_penalty", 0.0),
             repetition_penalty=opt("repetition_penalty", 1.0), logprobs=lp, n=opt("n", 1),
-            min_p=opt("min_p", 0.0), logit_bias=bias)
+            min_p=opt("min_p", 0.0), logit_bias=bias,
+            lora=body.get("model") if body.get("model") in self.lora_names else None)
         self._check_bias(params)
         return params
 
@@ -567,7 +572,7 @@ async def _collect(gens):
 
 
 async def serve(engine, host: str, port: int, model_name: str, ready: asyncio.Event | None = None,
-                extra_names: tuple = (), worker_procs=(), death_grace_s: float = 5.0):
+                extra_names: tuple = (), worker_procs=(), death_grace_s: float = 5.0, lora_names: tuple = ()):
     """Serve until the engine dies. ``worker_procs``: TP worker processes to watch;
     if one exits the engine is marked dead (/health 503) and this process exits
     after ``death_grace_s`` so Kubernetes restarts the pod."""
@@ -583,7 +588,7 @@ async def serve(engine, host: str, port: int, model_name: str, ready: asyncio.Ev
             on_death=lambda p: ae.mark_dead(EngineDeadError(
                 f"TP worker pid {getattr(p, 'pid', '?')} exited with code {getattr(p, 'exitcode', '?')}")))
         monitor.start()
-    srv = OpenAIServer(ae, model_name, engine.max_model_len, extra_names)
+    srv = OpenAIServer(ae, model_name, engine.max_model_len, extra_names, lora_names)
     runner = web.AppRunner(srv.app(), access_log=None)
     await runner.setup()
     site = web.TCPSite(runner, host, port, reuse_port=True, backlog=4096)

@@ -53,12 +53,27 @@ def build_parser(prog="hipserve") -> argparse.ArgumentParser:
                     help="MoE models at TP > 1: whole experts per rank instead of a width slice of each "
                          "(automatic where the width slice has no expert kernel, e.g. Qwen3-30B-A3B)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--enable-lora", action="store_true", help="serve the PEFT adapters of --lora-modules")
+    ap.add_argument("--lora-modules", nargs="*", default=[], metavar="NAME=PATH",
+                    help="adapters, all resident; a request selects one by its model name")
+    ap.add_argument("--max-loras", type=int, default=None, help="adapter slots (default: the adapters listed)")
+    ap.add_argument("--max-lora-rank", type=int, default=16, choices=[8, 16, 32, 64])
     ap.add_argument("--n-gpu-layers", "-ngl", dest="ngl", type=int, default=None,
                     help="accepted for llama-server compatibility (all layers always run on the GPU)")
     ap.add_argument("--log-level", default=os.environ.get("HIPSERVE_LOG_LEVEL", "INFO"))
     ap.add_argument("--log-format", default=None, choices=["text", "json"],
                     help="text (default) or one JSON object per line (HIPSERVE_LOG_FORMAT)")
     return ap
+
+
+def _lora_modules(items) -> dict:
+    out = {}
+    for it in items:
+        name, sep, path = it.partition("=")
+        if not sep or not name or not path or name in out:
+            raise ValueError(f"--lora-modules takes distinct NAME=PATH entries, got {it!r}")
+        out[name] = path
+    return out
 
 
 def config_from_args(a) -> EngineConfig:
@@ -81,6 +96,8 @@ def config_from_args(a) -> EngineConfig:
         enable_prefix_caching=a.enable_prefix_caching, enforce_eager=a.enforce_eager,
         enable_expert_parallel=getattr(a, "enable_expert_parallel", False), seed=a.seed,
         trust_remote_code=a.trust_remote_code, host=a.host, port=a.port,
+        enable_lora=a.enable_lora, lora_modules=_lora_modules(a.lora_modules), max_loras=a.max_loras,
+        max_lora_rank=a.max_lora_rank,
         extra={"quantization": a.quantization} if a.quantization else {})
 
 
@@ -132,7 +149,7 @@ def main(argv=None, prog="hipserve"):
     names = (cfg.model,) if cfg.served_model_name else ()
     try:
         asyncio.run(serve(engine, cfg.host, cfg.port, cfg.model_name, extra_names=names,
-                          worker_procs=procs))
+                          worker_procs=procs, lora_names=tuple(engine.lora_names)))
     finally:
         engine.shutdown()
         for p in procs:
