@@ -178,6 +178,18 @@ void launch_fill_uniform(void* out, long ld, int rows, int cols, long row0, long
 constexpr int DG_GLU = 1, DG_PARTIAL = 2;
 bool launch_decode_gemm(void* out, long out_stride, float* ws, const void* x, long x_stride, const void* w, int M,
                         int N, int K, int rt, int S, bool packed, int flags, hipStream_t s);
+// act[M, N/2] (bf16) = silu(bf16(sum gate)) * bf16(sum up) of the fp32 partials ws[S, M, N] of a
+// glu-packed weight (columns in the packed order: 64 gate then their 64 up per 128)
+void launch_splitk_reduce_glu(void* out, long out_stride, const float* ws, int M, int N, int S, hipStream_t s);
+
+// decode_gemm_wide.hip — the same GEMM for 65 <= M <= 256 on the packed layout only (flags and
+// output forms as launch_decode_gemm). nw: 128 / 256 weight rows per workgroup, mh: 1 / 2
+// M-halves (2 only above 128 rows; (128, 1) above 128 rows is refused). K % 256 == 0 and
+// K / S = 128 * a compiled half-step count (decode_gemm_wide_steps_ok); x_stride >= K, % 8 == 0. False when it cannot run.
+bool decode_gemm_wide_config_ok(int M, int nw, int mh);
+bool decode_gemm_wide_steps_ok(int half_steps);
+bool launch_decode_gemm_wide(void* out, long out_stride, float* ws, const void* x, long x_stride, const void* w, int M,
+                             int N, int K, int nw, int mh, int S, int flags, hipStream_t s);
 
 
 // prefill epilogues (prefill_gemm.hip FP8 kernel, prefill_gemm_packed.hip):

@@ -311,6 +311,13 @@ void launch_splitk_reduce(void* out, long out_stride, const float* ws, int M, in
   splitk_reduce_kernel<<<(n8 + 255) / 256, 256, 0, s>>>(static_cast<unsigned short*>(out), out_stride, ws, M, N, S);
 }
 
+void launch_splitk_reduce_glu(void* out, long out_stride, const float* ws, int M, int N, int S, hipStream_t s) {
+  const long n8 = (long)M * (N / 2) / 8;
+  if (n8 <= 0) return;
+  splitk_reduce_glu_kernel<<<(n8 + 255) / 256, 256, 0, s>>>(static_cast<unsigned short*>(out), out_stride, ws, M, N,
+                                                             S);
+}
+
 // rt 1: 8 waves x 1 row group, 2: 4 waves x 2 (both 128 weight rows per workgroup);
 // 3: 4 waves x 1 (64 rows: twice the workgroups at the same K split, for projections
 // whose 128-row tiles do not fill the chip without more split-K partials)

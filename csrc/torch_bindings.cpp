@@ -1003,6 +1003,74 @@ void decode_gemm_glu(at::Tensor& act, const at::Tensor& x, const at::Tensor& wp,
               "decode_gemm_glu: unsupported (rt, K/splits)");
 }
 
+// ---- the wide decode GEMM (decode_gemm_wide.hip): 65 <= M <= 256 rows on the packed layout.
+// nw: 128 / 256 weight rows per workgroup, mh: 1 / 2 M-halves; the three forms mirror
+// decode_gemm_packed / decode_gemm_partial (packed) / decode_gemm_glu.
+DecodeX decode_gemm_wide_x(const Args& a, const at::Tensor& x, int64_t nw, int64_t mh, int64_t splits) {
+  const void* p = a.ptr(x, "x", BF16, ROWS8, {ANY, ANY});
+  const int M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 65 && M <= 256, a.op, ": 65 <= M <= 256");
+  TORCH_CHECK(hipserve::decode_gemm_wide_config_ok(M, (int)nw, (int)mh), a.op,
+              ": (nw, mh) must be (128, 1) or (256, 1) up to 128 rows, (256, 1), (256, 2) or (128, 2) above");
+  TORCH_CHECK(K % 256 == 0 && splits >= 1 && K % (128 * splits) == 0, a.op,
+              ": K must be a multiple of 256 and of 128*splits");
+  TORCH_CHECK(hipserve::decode_gemm_wide_steps_ok(K / splits / 128), a.op,
+              ": unsupported K/splits: not 128 * a half-step count compiled in decode_gemm_wide.hip");
+  TORCH_CHECK(x.stride(0) * 512 < (1L << 31), a.op, ": x row stride too large for 32-bit byte offsets");
+  return {p, M, K, (long)x.stride(0)};
+}
+const void* wide_packed_w(const Args& a, const at::Tensor& wp, int64_t N, int K) {
+  return a.ptr(wp, "wp (pack_decode_weight)", BF16, CONTIG, exactly((N + 127) / 128 * 128 * K));
+}
+
+void decode_gemm_wide(at::Tensor& out, const at::Tensor& x, const at::Tensor& wp, at::Tensor& ws, int64_t N,
+                      int64_t nw, int64_t mh, int64_t splits) {
+  Args a("decode_gemm_wide", x, "x");
+  const DecodeX X = decode_gemm_wide_x(a, x, nw, mh, splits);
+  TORCH_CHECK(N % 8 == 0, "decode_gemm_wide: N % 8 == 0");
+  const void* wpp = wide_packed_w(a, wp, N, X.K);
+  void* op = a.ptr(out, "out", BF16, ROWS4, {X.M, N});
+  float* wsp = splits > 1 ? splitk_ws(a, ws, splits, X.M, N) : nullptr;
+  TORCH_CHECK(hipserve::launch_decode_gemm_wide(op, out.stride(0), wsp, X.p, X.stride, wpp, X.M, N, X.K, nw, mh, splits,
+                                                0, cur_stream()),
+              "decode_gemm_wide: unsupported launch");
+}
+
+void decode_gemm_wide_partial(at::Tensor& ws, const at::Tensor& x, const at::Tensor& wp, int64_t N, int64_t nw,
+                              int64_t mh, int64_t splits) {
+  Args a("decode_gemm_wide_partial", x, "x");
+  const DecodeX X = decode_gemm_wide_x(a, x, nw, mh, splits);
+  TORCH_CHECK(N % 8 == 0, "decode_gemm_wide_partial: N % 8 == 0");
+  const void* wpp = wide_packed_w(a, wp, N, X.K);
+  float* wsp = splitk_ws(a, ws, splits, X.M, N);
+  TORCH_CHECK(hipserve::launch_decode_gemm_wide(nullptr, N, wsp, X.p, X.stride, wpp, X.M, N, X.K, nw, mh, splits,
+                                                hipserve::DG_PARTIAL, cur_stream()),
+              "decode_gemm_wide_partial: unsupported launch");
+}
+
+void decode_gemm_wide_glu(at::Tensor& act, const at::Tensor& x, const at::Tensor& wp, at::Tensor& ws, int64_t N,
+                          int64_t nw, int64_t mh, int64_t splits) {
+  Args a("decode_gemm_wide_glu", x, "x");
+  const DecodeX X = decode_gemm_wide_x(a, x, nw, mh, splits);
+  TORCH_CHECK(N % 128 == 0, "decode_gemm_wide_glu: N % 128 == 0");
+  const void* wpp = a.ptr(wp, "wp (pack_decode_weight, glu)", BF16, CONTIG, exactly(N * X.K));
+  void* ap = a.ptr(act, "act", BF16, ROWS8, {X.M, N / 2});
+  float* wsp = splits > 1 ? splitk_ws(a, ws, splits, X.M, N) : nullptr;
+  TORCH_CHECK(hipserve::launch_decode_gemm_wide(ap, act.stride(0), wsp, X.p, X.stride, wpp, X.M, N, X.K, nw, mh, splits,
+                                                hipserve::DG_GLU, cur_stream()),
+              "decode_gemm_wide_glu: unsupported launch");
+}
+
+// act [M, N/2] = silu(bf16(sum gate)) * bf16(sum up) of glu-packed partials ws [S, M, N]
+void splitk_reduce_glu(at::Tensor& act, const at::Tensor& ws, int64_t splits) {
+  Args a("splitk_reduce_glu", act, "act");
+  void* ap = a.ptr(act, "act", BF16, ROWS8, {ANY, ANY});
+  const int M = act.size(0), I = act.size(1);
+  TORCH_CHECK(I % 64 == 0, "splitk_reduce_glu: N/2 % 64 == 0");
+  hipserve::launch_splitk_reduce_glu(ap, act.stride(0), splitk_ws(a, ws, splits, M, 2L * I), M, 2 * I, splits,
+                                     cur_stream());
+}
+
 // Prefill GEMM over the packed decode layout (prefill_gemm_packed.hip): wp =
 // pack_decode_weight(w[N, K], glu) (flat, ceil(N/128)*128*K bf16). epi as the FP8 prefill GEMM (PG_EPI_*)
 // (2 / 3 need the glu packing); bias (epi 0 only) bf16 [N] or None; wm 1 or 2.
@@ -1454,6 +1522,10 @@ void vision_pool_rmsnorm(at::Tensor& out, const at::Tensor& x, const at::Tensor&
   X(pack_decode_weight, "(Tensor(a!) out, Tensor w, bool glu=False) -> ()") \
   X(decode_gemm_partial, "(Tensor(a!) ws, Tensor x, Tensor w, int N, int rt, int splits, bool packed) -> ()") \
   X(decode_gemm_glu, "(Tensor(a!) act, Tensor x, Tensor wp, Tensor(b!) ws, int N, int rt, int splits) -> ()") \
+  X(decode_gemm_wide, "(Tensor(a!) out, Tensor x, Tensor wp, Tensor(b!) ws, int N, int nw, int mh, int splits) -> ()") \
+  X(decode_gemm_wide_partial, "(Tensor(a!) ws, Tensor x, Tensor wp, int N, int nw, int mh, int splits) -> ()") \
+  X(decode_gemm_wide_glu, "(Tensor(a!) act, Tensor x, Tensor wp, Tensor(b!) ws, int N, int nw, int mh, int splits) -> ()") \
+  X(splitk_reduce_glu, "(Tensor(a!) act, Tensor ws, int splits) -> ()") \
   X(prefill_gemm_packed, "(Tensor(a!) out, Tensor x, Tensor wp, int N, int epi, Tensor? bias=None, int wm=1, int grid=0, int rw=4) -> ()") \
   X(prefill_gemm_packed_grouped, "(Tensor(a!) out, Tensor x, Tensor wp, int N, int epi, Tensor tile_expert, Tensor num_tiles, int wm=1, int rw=4, Tensor? gather_slots=None, int gather_k=1) -> ()") \
   X(prefill_gemm_f8, "(Tensor(a!) out, Tensor xq, Tensor xs, Tensor[] q, Tensor[] rs, int epi) -> ()") \

@@ -190,9 +190,13 @@ class ModelRunner:
             from ..ops import gemm
 
             ms = [b for b in self.buckets if b <= 64]
+            # buckets of 65-256 rows: the wide decode GEMM's row counts that some bucket uses
+            # (nothing new is timed up to max_num_seqs 64)
+            ms += [m for lo, m in zip((64,) + gemm.WIDE_MS, gemm.WIDE_MS) if self.buckets[-1] > lo]
             self.model.fused_decode = bool(ecfg.extra.get("fused_decode",
                                                           os.environ.get("HIPSERVE_FUSED_DECODE", "1") != "0"))
             fused = self.model.fused_gemm_shapes() if self.model.fused_decode else {}
+            gemm.TUNER.wide_fused = tp.world_size == 1  # TP > 1: only the plain bf16-output form above 64 rows
             self.gemm_report = gemm.TUNER.tune(self.model.gemm_shapes(), self.device, ms, fused=fused)
             self.single_layout = None
             if ecfg.extra.get("packed_decode", True):

@@ -909,7 +909,7 @@ class LlamaModel(MoEMixin):
                 continue
             gelu = cfg.hidden_act == "gelu_tanh"
             lgu = lo is not None and lo.has(i, "gu")  # no GLU-in-epilogue form: it has no pre-activation output
-            gc = None if gelu or lgu else gemm.glu_choice(T, lw.wgu)
+            gc = None if gelu or lgu or not self._wide_fused_ok(T) else gemm.glu_choice(T, lw.wgu)
             pt = (None if gc is not None or (isinstance(lw.wgu, torch.Tensor) and not gelu)
                   else self._partial(xn, lw.wgu, xn16, xn8))
             act16 = None
@@ -971,6 +971,8 @@ class LlamaModel(MoEMixin):
         ``QuantWeight`` (``x16``: the producer's f16 copy of x, see ``_x16``); None
         when the projection runs unfused (hipBLASLt choice)."""
         if isinstance(w, (torch.Tensor, gemm.PackedLinear)):
+            if not self._wide_fused_ok(x.shape[0]):
+                return None
             fc = gemm.fused_choice(x.shape[0], w)
             return gemm.gemm_partial(x, w, fc) if fc is not None else None
         M = x.shape[0]
@@ -979,6 +981,12 @@ class LlamaModel(MoEMixin):
                 M <= Q.F8_DECODE_MAX_M and self.tp.world_size == 1 and Q.f8_decode_ok(w))):
             return Q.quant_partial(x, w, x16, x8)
         return None
+
+    def _wide_fused_ok(self, M: int) -> bool:
+        """Above 64 rows (the wide bf16 decode GEMM) the fused units run at TP = 1 only: the
+        cross-rank epilogues are sized for <= 64 rows, so TP > 1 takes the plain bf16-output
+        form through ``linear``."""
+        return M <= 64 or self.tp.world_size == 1
 
     X16 = os.environ.get("HIPSERVE_QGEMM_X16", "1") != "0"
     # (a split-K GLU -> e4m3 act kernel, one block per row, measured slower than splitk_glu's

@@ -12,6 +12,7 @@ real decode step streams from HBM once per layer.
 from __future__ import annotations
 
 import logging
+import os
 import weakref
 
 import torch
@@ -38,6 +39,11 @@ TC_KIND = "decode_gemm_cold2"  # tuning-cache kind: bumped when the timing metho
 # epilogue, and only timing both units picks the split count that is really best.
 _EMPTY = {}
 TUNE_MS = [1, 2, 4, 8, 16, 24, 32, 48, 64]
+# the wide decode GEMM (csrc/kernels/decode_gemm_wide.hip, choice ("dgw", nw, mh, S)): decode
+# buckets of 65-256 rows are tuned at these row counts, a bucket M using the smallest entry >= M
+WIDE_MS = (128, 256)
+WIDE_STEPS = [1, 2, 4, 7, 8, 14, 16, 28, 32]  # 128-k half-steps per workgroup (compile-time there)
+WIDE = os.environ.get("HIPSERVE_WIDE_GEMM", "1") != "0"  # 0: hipBLASLt above 64 rows, as before (A/B)
 
 
 class GemmTuner:
@@ -47,13 +53,17 @@ class GemmTuner:
         # for weights kept only in the packed layout (PackedLinear)
         self.best_packed: dict[tuple, tuple] = {}
         self.report: list[dict] = []
+        self.wide_fused = True  # rows above 64 are tuned as GEMM + epilogue units (the engine: TP = 1 only)
 
     def packed_shapes(self) -> set:
         """(N, K) whose tuned choice uses the packed layout at some M."""
-        return {(N, K) for (M, N, K), c in self.table.items() if isinstance(c, tuple) and c[0] == "dgp"}
+        return {(N, K) for (M, N, K), c in self.table.items() if isinstance(c, tuple) and c[0] in ("dgp", "dgw")}
 
     def choose(self, M: int, N: int, K: int):
-        if M > 64:
+        if M > 64:  # the wide table: empty (hipBLASLt) unless tune() was given wide row counts
+            for m in WIDE_MS if WIDE else ():
+                if m >= M:
+                    return self.table.get((m, N, K), "blas")
             return "blas"
         for m in TUNE_MS:
             if m >= M:
@@ -113,19 +123,26 @@ class GemmTuner:
         """fused: {(N, K): spec} for projections whose output feeds a fused
         epilogue in the decode layer — ("norm",), ("rope", nq, nkv, D, mode), ("attn", nq,
         nkv, D, mode) (the fused decode attention reads the partials: GEMM alone) or
-        ("glu",); those are timed as GEMM + epilogue units."""
+        ("glu",); those are timed as GEMM + epilogue units. Row counts in WIDE_MS time the
+        wide decode GEMM's candidates the same way (``self.wide_fused`` False: as plain
+        GEMMs — TP > 1, whose cross-rank epilogues stop at 64 rows)."""
         # inference mode like the engine's graph capture: the generator state tensors a
         # capture registers must not switch between inference and normal tensors
         from . import tune_cache as TC
 
         fused = fused or {}
-        ms = [m for m in (ms or TUNE_MS) if m <= 64]
+        ms = [m for m in (ms or TUNE_MS) if m <= 64 or (WIDE and m in WIDE_MS)]
         for (N, K) in sorted(set(shapes)):
-            spec = fused.get((N, K))
+            spec0 = fused.get((N, K))
+            specs = {M: spec0 if M <= 64 or self.wide_fused else None for M in ms}
+            glu = spec0 is not None and spec0[0] == "glu"
+            # a GLU-interleaved copy has no plain x W^T: a wide row of a gate|up shape that may
+            # not run its GLU unit (TP > 1) is neither timed nor cached and stays on hipBLASLt
+            tms = [M for M in ms if not (glu and specs[M] is None)]
             # a previous start on this device and kernel build timed this shape: reuse it
-            hits = [TC.get(device, TC_KIND, [M, N, K, spec]) for M in ms]
+            hits = [TC.get(device, TC_KIND, [M, N, K, specs[M]]) for M in tms]
             if all(h is not None for h in hits):
-                for M, h in zip(ms, hits):
+                for M, h in zip(tms, hits):
                     self.table[(M, N, K)] = TC.tup(h["best"])
                     if h["bp"] is not None:
                         self.best_packed[(M, N, K)] = (TC.tup(h["bp"][0]), h["bp"][1])
@@ -136,10 +153,10 @@ class GemmTuner:
             # missed what the engine sees between two uses of a layer (10.7 us, cold)
             ncopy = max(1, min(COLD_COPIES_MAX, -(-COLD_BYTES // (N * K * 2))))
             ws_ = [torch.randn(N, K, device=device, dtype=torch.bfloat16) for _ in range(ncopy)]
-            glu = spec is not None and spec[0] == "glu"
             wp_ = [pack(w, glu=glu) for w in ws_] if packable(N, K) and (not glu or N % 128 == 0) else None
             n = max(16, ncopy)
-            for M in ms:
+            for M in tms:
+                spec = specs[M]
                 x = torch.randn(M, K, device=device, dtype=torch.bfloat16)
                 out = torch.empty(M, N, device=device, dtype=torch.bfloat16)
                 unit = _Unit(spec, M, N, device) if spec else None
@@ -148,7 +165,9 @@ class GemmTuner:
                 best, best_t = "blas", self._time(blas_fn, n=n)
                 t_blas = best_t
                 timed = []
-                for cfg in self.candidates(M, N, K, packed=wp_ is not None, glu=glu):
+                cands = self.candidates(M, N, K, packed=wp_ is not None, glu=glu) if M <= 64 else \
+                    self.wide_candidates(M, N, K, glu=glu) if wp_ is not None else []
+                for cfg in cands:
                     if unit is not None:
                         if cfg[0] == "sk":
                             continue
@@ -215,6 +234,25 @@ class GemmTuner:
                 out.append(("sk", rt, kw))
         return out
 
+    @staticmethod
+    def wide_candidates(M, N, K, glu=False):
+        """("dgw", nw, mh, S) for a row count in WIDE_MS: every (nw, mh) the kernel runs at M,
+        each with the split that first fills the 256 CUs and its two neighbours. A split whose
+        fp32 partials (S M N 4 bytes) outweigh the weight (N K 2) is pruned: small-N
+        projections fill the chip with M-halves and 128-row workgroups before split-K."""
+        out = []
+        if K % 256 or N % (128 if glu else 8):
+            return out
+        for nw, mh in ([(128, 1), (256, 1)] if M <= 128 else [(128, 2), (256, 2), (256, 1)]):
+            tiles = -(-N // nw)
+            ss = [S for S in range(1, K // 128 + 1)
+                  if K % (128 * S) == 0 and K // (128 * S) in WIDE_STEPS and (S == 1 or S * M * 4 <= K * 2)]
+            if not ss:
+                continue
+            fill = next((i for i, S in enumerate(ss) if tiles * S * mh >= 256), len(ss) - 1)
+            out += [("dgw", nw, mh, S) for S in ss[max(0, fill - 1):fill + 2]]
+        return out[:10]
+
 
 class _Unit:
     """A decode GEMM together with the op its output feeds, for tuning: the
@@ -254,6 +292,15 @@ class _Unit:
 
     def fused(self, cfg, x, w, wp):
         op, M, N = self.op, self.M, self.N
+        if cfg[0] == "dgw":  # the wide GEMM: GLU form, or partials into the same epilogues
+            _, nw, mh, S = cfg
+            if self.kind == "glu":
+                ws = torch.empty(S * M * N, dtype=torch.float32, device=x.device) if S > 1 else \
+                    _empty(x.device)[1]
+                return op.decode_gemm_wide_glu(self.act, x, wp, ws, N, nw, mh, S)
+            ws = torch.empty(S * M * N, dtype=torch.float32, device=x.device)
+            op.decode_gemm_wide_partial(ws, x, wp, N, nw, mh, S)
+            return self.epilogue(ws, S)
         kind, rt, S = cfg
         packed = kind == "dgp" and wp is not None
         if self.kind == "glu":
@@ -268,6 +315,10 @@ class _Unit:
             return
         ws = torch.empty(S * M * N, dtype=torch.float32, device=x.device)
         op.decode_gemm_partial(ws, x, wp if packed else w, N, rt, S, packed)
+        self.epilogue(ws, S)
+
+    def epilogue(self, ws, S):
+        op = self.op
         if self.kind == "norm":
             op.splitk_add_rmsnorm(self.y, self.res, ws, S, self.w, 1e-5)
         elif self.kind == "attn":
@@ -407,14 +458,36 @@ def decode_gemm_packed(out, x, wp, N, rt, splits):
     return out
 
 
+def decode_gemm_wide(out, x, wp, N, nw, mh, splits):
+    M = x.shape[0]
+    ws = (torch.empty(splits * M * N, dtype=torch.float32, device=x.device) if splits > 1
+          else _empty(x.device)[1])
+    torch.ops.hipserve.decode_gemm_wide(out, x, wp, ws, N, nw, mh, splits)
+    return out
+
+
+def wide_choice(M: int, w, glu: bool = False):
+    """(("dgw", nw, mh, S), packed weight) when the tuner picked the wide decode GEMM for
+    ``w`` at 64 < M <= 256 and its (GLU-)packed copy exists; None: hipBLASLt / packed prefill."""
+    if not 64 < M <= 256 or not TUNER.table:
+        return None
+    c = TUNER.choose(M, w.shape[0], w.shape[1])
+    if not isinstance(c, tuple) or c[0] != "dgw":
+        return None
+    wp = glu_of(w) if glu else packed_of(w)
+    return None if wp is None else (c, wp)
+
+
 def fused_choice(M: int, w):
     """(choice, packed weight or None) when the tuned decode GEMM for ``w`` at M can
     write split-K partials for a fused epilogue; None for hipBLASLt / skinny."""
+    if M > 64:
+        return wide_choice(M, w) if isinstance(w, (torch.Tensor, PackedLinear)) else None
     if isinstance(w, PackedLinear):
-        if M > 64 or w.glu:
+        if w.glu:
             return None
         return TUNER.choose_packed(M, w.N, w.K), w.wp
-    if not isinstance(w, torch.Tensor) or M > 64 or not TUNER.table:
+    if not isinstance(w, torch.Tensor) or not TUNER.table:
         return None
     c = TUNER.choose(M, w.shape[0], w.shape[1])
     if not isinstance(c, tuple) or c[0] not in ("dg", "dgp"):
@@ -425,8 +498,13 @@ def fused_choice(M: int, w):
 
 def gemm_partial(x, w, fc):
     """Run fused_choice ``fc`` on x writing fp32 partials; returns (ws, S)."""
-    (kind, rt, S), wp = fc
     M, N = x.shape[0], w.shape[0]
+    if fc[0][0] == "dgw":
+        (_, nw, mh, S), wp = fc
+        ws = torch.empty(S * M * N, dtype=torch.float32, device=x.device)
+        torch.ops.hipserve.decode_gemm_wide_partial(ws, x, wp, N, nw, mh, S)
+        return ws, S
+    (kind, rt, S), wp = fc
     ws = torch.empty(S * M * N, dtype=torch.float32, device=x.device)
     packed = wp is not None
     torch.ops.hipserve.decode_gemm_partial(ws, x, wp if packed else w, N, rt, S, packed)
@@ -435,13 +513,17 @@ def gemm_partial(x, w, fc):
 
 def glu_choice(M: int, w):
     """(rt, S, glu-packed weight) when the tuned decode GEMM for the merged gate|up
-    weight ``w`` at M is the packed kernel and a GLU-interleaved copy exists."""
+    weight ``w`` at M is the packed kernel and a GLU-interleaved copy exists; above 64
+    rows (nw, mh, S, glu-packed weight) of the wide kernel."""
+    if M > 64:
+        wc = wide_choice(M, w, glu=True) if isinstance(w, (torch.Tensor, PackedLinear)) else None
+        return None if wc is None else (*wc[0][1:], wc[1])
     if isinstance(w, PackedLinear):
-        if M > 64 or not w.glu:
+        if not w.glu:
             return None
         c = TUNER.choose_packed(M, w.N, w.K)
         return c[1], c[2], w.wp
-    if not isinstance(w, torch.Tensor) or M > 64 or not TUNER.table:
+    if not isinstance(w, torch.Tensor) or not TUNER.table:
         return None
     c = TUNER.choose(M, w.shape[0], w.shape[1])
     wp = glu_of(w)
@@ -452,15 +534,20 @@ def glu_choice(M: int, w):
 
 def gemm_glu(x, w, gc):
     """act[M, N/2] = silu(x Wg^T) * (x Wu^T) in one decode GEMM (+ GLU reduce if S > 1)."""
-    rt, S, wp = gc
+    *cfg, S, wp = gc  # cfg: (rt,), or (nw, mh) of the wide kernel
     M, N = x.shape[0], w.shape[0]
     act = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
     ws = (torch.empty(S * M * N, dtype=torch.float32, device=x.device) if S > 1 else _empty(x.device)[1])
-    torch.ops.hipserve.decode_gemm_glu(act, x, wp, ws, N, rt, S)
+    if len(cfg) == 2:
+        torch.ops.hipserve.decode_gemm_wide_glu(act, x, wp, ws, N, cfg[0], cfg[1], S)
+    else:
+        torch.ops.hipserve.decode_gemm_glu(act, x, wp, ws, N, cfg[0], S)
     return act
 
 
 def run_choice(c, out, x, w, wp=None):
+    if c[0] == "dgw":  # packed layout only: linear() takes hipBLASLt for a weight without the copy
+        return decode_gemm_wide(out, x, wp if wp is not None else packed_of(w), out.shape[1], c[1], c[2], c[3])
     if c[0] == "dgp":
         if wp is None:
             wp = packed_of(w)
@@ -499,7 +586,7 @@ def packed_prefill(x: torch.Tensor, w: PackedLinear, epi: int = 0, out: torch.Te
 
 def packed_linear(x: torch.Tensor, w: PackedLinear) -> torch.Tensor:
     """out = x W^T for a packed-only (non-GLU) weight: the packed decode GEMM up to 64
-    rows, the packed prefill GEMM above."""
+    rows, the wide one up to 256 where the tuner picked it, the packed prefill GEMM else."""
     assert not w.glu, "a GLU-interleaved weight has no plain x W^T (use packed_glu)"
     M = x.shape[0]
     if x.stride(1) != 1 or x.stride(0) % 8:
@@ -508,6 +595,10 @@ def packed_linear(x: torch.Tensor, w: PackedLinear) -> torch.Tensor:
         c = TUNER.choose_packed(M, w.N, w.K)
         out = torch.empty(M, w.N, device=x.device, dtype=x.dtype)
         return decode_gemm_packed(out, x, w.wp, w.N, c[1], c[2])
+    wc = wide_choice(M, w)
+    if wc is not None:
+        out = torch.empty(M, w.N, device=x.device, dtype=x.dtype)
+        return run_choice(wc[0], out, x, w, wc[1])
     return packed_prefill(x, w)
 
 
@@ -520,6 +611,9 @@ def packed_glu(x: torch.Tensor, w: PackedLinear, gelu: bool = False) -> torch.Te
     if M <= 64 and not gelu:
         c = TUNER.choose_packed(M, w.N, w.K)
         return gemm_glu(x, w, (c[1], c[2], w.wp))
+    gc = None if gelu else glu_choice(M, w)
+    if gc is not None:
+        return gemm_glu(x, w, gc)
     return packed_prefill(x, w, 3 if gelu else 2)
 
 
@@ -527,9 +621,9 @@ def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     if isinstance(w, PackedLinear):
         return packed_linear(x, w)
     M = x.shape[0]
-    if M <= 64 and x.is_cuda and TUNER.table:
+    if M <= 256 and x.is_cuda and TUNER.table:
         c = TUNER.choose(M, w.shape[0], w.shape[1])
-        if c != "blas" and x.stride(1) == 1 and x.stride(0) % 8 == 0:
+        if c != "blas" and x.stride(1) == 1 and x.stride(0) % 8 == 0 and (c[0] != "dgw" or packed_of(w) is not None):
             out = torch.empty(M, w.shape[0], device=x.device, dtype=x.dtype)
             return run_choice(c, out, x, w)
     return F.linear(x, w)
