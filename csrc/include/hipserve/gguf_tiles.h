@@ -24,6 +24,9 @@ namespace gq {
 // Q2_K / Q3_K: the 2-bit / 3-bit K-quants (16-element sub-blocks like Q6_K): Q2_K
 // w = d sc q - dmin m with 4-bit sc, m per sub-block; Q3_K w = d (s - 32) (q - 4) with a
 // 6-bit scale s per sub-block and the third bit of q in a separate plane (hmask).
+// IQ4_NL / IQ4_XS: the 4-bit codebook formats, w = s kvalues[nibble] with a fixed non-linear
+// table of 16 signed bytes (kIq4T); s = d per 32 k (IQ4_NL), d (ls - 32) with a 6-bit ls per
+// 32 k and an f16 d per 256 k (IQ4_XS). The nibbles sit in Q4_0's arrangement.
 // (the enum and what is true of each format: quant_formats.h, one table row per format)
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -95,6 +98,14 @@ struct Raw {
 //         int8 s - 32 at load (4 bytes per row and super-block more than the file: the
 //         in-kernel 6-bit unpack is the VALU cost that bounds this kernel family); its
 //         hmask bytes 16 (g & 1) .. + 15 hold the third bit of step s at bit 4 (g >> 1) + (s >> 1)
+//   IQ4_NL [2 x 64 lanes x 16 qs][16 rows x 8 d]                    2304 B (Q4_0's chunk)
+//   IQ4_XS [2 x 64 lanes x 16 qs][16 rows x 8 int8 (ls - 32)][16 rows x d]      2208 B
+//         both: load j of lane 16 g + c is the 16 qs bytes of the row's 32-k block 2 g + j
+//         (IQ4_XS: sub-block 2 g + j of the super-block), low nibbles k 0-15, high 16-31 of
+//         it, so Q4_0's words, shifts and kbase pick the nibbles. IQ4_XS's 6-bit sub-block
+//         scales (4 low bits in scales_l, 2 high in scales_h) are unpacked to int8 ls - 32
+//         at load, as Q3_K's: 4.3125 bits per weight resident against the file's 4.25; a
+//         lane reads its two as one ushort at 2048 + 8 c + 2 g, d at 2176 + 2 c
 template <int QT>
 constexpr int chunk_bytes() { return quant_format(QT).chunk_bytes; }
 // formats whose per-row scale (Part::rs) multiplies the accumulators in the epilogue
@@ -187,7 +198,12 @@ HS_DEVICE void load_raw(const unsigned char* ch, int g, int c, int lane, Raw& r)
     const unsigned dd = *reinterpret_cast<const unsigned*>(ch + 4096 + 16 * c + 4 * g);
     r.h[0] = dd & 0xFFFF;
     r.h[1] = dd >> 16;
-  } else {  // Q4_0 / Q4_1
+  } else if constexpr (QT == IQ4_XS) {
+    r.v[0] = ld16(ch + 16 * lane);
+    r.v[1] = ld16(ch + 1024 + 16 * lane);
+    r.h[0] = *reinterpret_cast<const unsigned short*>(ch + 2176 + 2 * c);          // d
+    r.h[1] = *reinterpret_cast<const unsigned short*>(ch + 2048 + 8 * c + 2 * g);  // ls - 32 of sub-blocks 2g, 2g + 1
+  } else {  // Q4_0 / Q4_1 / IQ4_NL
     r.v[0] = ld16(ch + 16 * lane);
     r.v[1] = ld16(ch + 1024 + 16 * lane);
     const unsigned dd = *reinterpret_cast<const unsigned*>(ch + 2048 + 16 * c + 4 * g);
@@ -245,6 +261,8 @@ HS_DEVICE int kbase(int g, int s) {
 // it to the v1 kernel. Q2_K (q < 4) takes the highest shift that keeps q << kSub below
 // 1024, 8: d sc < 65504 / 2^16 ~ 0.9995; Q3_K (q < 8) 7: |d (s - 32)| < 65504 / 2^17 ~ 0.4998.
 // These two have no v1 kernel: a weight beyond the range is held as bf16 (QuantWeight.from_gguf).
+// IQ4_NL / IQ4_XS enter as the biased byte u = kvalues[nibble] + 128 in [1, 241] at Q8_0's
+// shift 2 with Q8_0's addend -128 s: |s| < 0.0156, s = d / d (ls - 32); no v1 kernel either.
 template <int QT>
 constexpr int sub_shift() { return quant_format(QT).sub_shift; }
 template <int QT>
@@ -252,7 +270,27 @@ constexpr float sub_up() {
   return gguf_block_format(QT) ? (float)(1 << (24 - sub_shift<QT>())) : 1.f;
 }
 template <int QT>
-constexpr float sub_zero() { return QT == Q4_0 ? -8.f : QT == Q6_K ? -32.f : QT == Q8_0 ? -128.f : QT == Q3_K ? -4.f : 0.f; }
+constexpr float sub_zero() {
+  return QT == Q4_0 ? -8.f : QT == Q6_K ? -32.f : QT == Q8_0 || QT == IQ4_NL || QT == IQ4_XS ? -128.f : QT == Q3_K ? -4.f : 0.f;
+}
+
+// IQ4_NL / IQ4_XS codebook, biased: byte i of word j is kvalues[4 j + i] + 128, kvalues =
+// {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}
+constexpr unsigned kIq4T[4] = {0x3F2D1801u, 0x766A5D4Fu, 0xA6998D81u, 0xF1D9C5B5u};
+// The four nibbles at bit sh of the bytes of w -> their four biased table bytes, in place.
+// The table stays in 4 wave-uniform registers and is applied a word at a time: the low 3
+// bits of every nibble are the v_perm_b32 selector into entries 0-7 and into entries 8-15
+// (a selector byte 0-3 picks from the second operand, 4-7 from the first), and a third
+// v_perm_b32 takes each byte from the first or the second result by bit 3 of its nibble
+// (selector byte i = i + 4 bit3). 6 VALU ops per 4 weights (7 for the high nibbles); no
+// lane-indexed register array, no memory table.
+HS_DEVICE unsigned iq4_bytes(unsigned w, int sh) {
+  const unsigned n = w >> sh;
+  const unsigned sel = n & 0x07070707u;
+  const unsigned lo = __builtin_amdgcn_perm(kIq4T[1], kIq4T[0], sel);
+  const unsigned hi = __builtin_amdgcn_perm(kIq4T[3], kIq4T[2], sel);
+  return __builtin_amdgcn_perm(hi, lo, ((n >> 1) & 0x04040404u) | 0x03020100u);
+}
 
 // Q2_K / Q3_K: 2-bit fields at bit 2 j of bytes (0, 2) / (1, 3) of w moved to bit S of each half
 template <int S>
@@ -311,6 +349,10 @@ struct Dec {
       fcA = h2f(r.s2[0] >> 16);
       fdB = h2f(r.s2[1] & 0xFFFF);
       fcB = h2f(r.s2[1] >> 16);
+    } else if constexpr (QT == IQ4_XS) {  // d (ls - 32) of sub-blocks 2g / 2g + 1, formed in fp32 like Q4_K's d sc
+      const float d = h2f(r.h[0]);
+      fdA = d * (float)(signed char)(r.h[1] & 0xFF);
+      fdB = d * (float)(signed char)(r.h[1] >> 8);
     } else {
       fdA = h2f(r.h[0]);
       fdB = h2f(r.h[1]);
@@ -325,7 +367,13 @@ struct Dec {
     constexpr float up = sub_up<QT>(), zp = sub_zero<QT>();
     dA = splat(fdA * up);
     dB = splat(fdB * up);
-    if constexpr (QT == Q4_0 || QT == Q8_0) {
+    if constexpr (QT == IQ4_NL || QT == IQ4_XS) {
+      // -128 times the scale AS THE MULTIPLIER HOLDS IT: where s is an f16 subnormal (an IQ4_XS
+      // sub-block with a small ls - 32) f16(s 2^22) keeps bits that f16(s) drops, and the
+      // codebook's bias of 128 would multiply that difference into every weight
+      cA = splat(zp / up * (float)dA[0]);
+      cB = splat(zp / up * (float)dB[0]);
+    } else if constexpr (QT == Q4_0 || QT == Q8_0) {
       cA = splat(zp * (float)(_Float16)fdA);
       cB = splat(zp * (float)(_Float16)fdB);
     } else {
@@ -443,6 +491,13 @@ struct Dec {
       byte_pairs(wa, p[0], p[1]);
       byte_pairs(wb, p[2], p[3]);
       z = (_Float16)1152.f;  // int8 value
+    } else if constexpr (QT == IQ4_NL || QT == IQ4_XS) {  // Q4_0's words; the table byte of each nibble
+      const u32x4 v[2] = {r.v[0], r.v[1]};
+      const int blk = s >> 2, e = s & 3;
+      const int sh = e < 2 ? 0 : 4;
+      byte_pairs(iq4_bytes(word(v, 4 * blk + 2 * (e & 1)), sh), p[0], p[1]);
+      byte_pairs(iq4_bytes(word(v, 4 * blk + 2 * (e & 1) + 1), sh), p[2], p[3]);
+      z = (_Float16)1152.f;  // kvalues = table byte - 128
     } else {  // Q4_0 / Q4_1: block (s >> 2); elements 0-15 low nibbles, 16-31 high
       const u32x4 v[2] = {r.v[0], r.v[1]};
       const int blk = s >> 2, e = s & 3;
@@ -513,6 +568,17 @@ struct Dec {
         hbit_pairs<S>(hm[2 * (s & 1)], j, p[0], p[1]);
         hbit_pairs<S>(hm[2 * (s & 1) + 1], j, p[2], p[3]);
       }
+    } else if constexpr (QT == IQ4_NL || QT == IQ4_XS) {  // table byte kvalues + 128 in [1, 241], as Q8_0's
+      const u32x4 v[2] = {r.v[0], r.v[1]};
+      const int blk = s >> 2, e = s & 3;
+      const int sh = e < 2 ? 0 : 4;
+      const unsigned wa = iq4_bytes(word(v, 4 * blk + 2 * (e & 1)), sh);
+      const unsigned wb = iq4_bytes(word(v, 4 * blk + 2 * (e & 1) + 1), sh);
+      constexpr unsigned m = 0x00FF00FFu << S;
+      p[0] = (wa << S) & m;
+      p[1] = (wa >> (8 - S)) & m;
+      p[2] = (wb << S) & m;
+      p[3] = (wb >> (8 - S)) & m;
     } else {  // Q8_0: int8 + 128 in [0, 255]
       const u32x4 qv[4] = {r.v[0], r.v[1], r.v[2], r.v[3]};
       const unsigned wa = qv[s >> 1][2 * (s & 1)] ^ 0x80808080u, wb = qv[s >> 1][2 * (s & 1) + 1] ^ 0x80808080u;
@@ -534,7 +600,7 @@ struct Dec {
         scale(r, g, s, d, c);
         dd = splat(d * sub_up<QT>());
         cc = splat(QT == Q2_K ? c : sub_zero<QT>() * (float)(_Float16)d);
-      } else if constexpr (QT == Q4_0 || QT == Q4_1) {
+      } else if constexpr (QT == Q4_0 || QT == Q4_1 || QT == IQ4_NL || QT == IQ4_XS) {
         dd = (s >> 2) ? dB : dA;
         cc = (s >> 2) ? cB : cA;
       } else {

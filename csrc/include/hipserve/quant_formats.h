@@ -28,7 +28,9 @@ namespace gq {
   X(INT8C, 9, 4096, -1, false, true, false, true)  \
   X(INT4, 10, 2560, -1, false, false, false, true) \
   X(Q2_K, 11, 1344, 8, true, false, false, true)   \
-  X(Q3_K, 12, 1824, 7, true, false, false, true)
+  X(Q3_K, 12, 1824, 7, true, false, false, true)   \
+  X(IQ4_NL, 14, 2304, 2, true, false, false, true) \
+  X(IQ4_XS, 15, 2208, 2, true, false, false, true)
 
 struct QuantFormat {
   const char* name;

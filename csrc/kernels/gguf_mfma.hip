@@ -394,6 +394,8 @@ void launch_t(void* out, long out_stride, float* ws, const void* x, long x_strid
 // INT4 carries INT8's table with Q4_1's bytes: unconstrained like both (profiles/int4_resources.md)
 // Q2_K / Q3_K are GGUF blocks with a per-step scale like Q6_K: unconstrained too
 // (profiles/q2k_q3k_resources.md)
+// IQ4_NL / IQ4_XS carry Q4_0's bytes and scale table plus the codebook lookup: unconstrained, and the
+// 16-slot bodies reach 4 waves per SIMD unforced (profiles/iq4_resources.md)
 template <int QT, int MT>
 constexpr int qmoe_waves() {
   return !row_scaled<QT>() ? 1 : MT == 1 ? 4 : 1;  // row-scaled: no scale table in the chunk
@@ -887,7 +889,7 @@ bool launch_qmoe_gemm(void* out, long out_stride, float* ws, const void* x, long
 // Prefill GEMM over tiled GGUF parts (qpg_kernel) on x16 / rsc from launch_x_f16_pairs
 // (row stride K). STORE: out[:, col .. col + rows) per
 // part; ADD: out is the residual (updated in place); GLU / GEGLU: parts 0 / 1 are gate / up
-// (same format and rows), out[M, rows] = act(gate) * up. Formats: qpg_format() (Q4_0 .. Q6_K; not Q2_K / Q3_K);
+// (same format and rows), out[M, rows] = act(gate) * up. Formats: qpg_format() (Q4_0 .. Q6_K; not Q2_K / Q3_K / IQ4_NL / IQ4_XS);
 // a mix of formats launches once per format (one body per launch: a two-format kernel
 // spills). Returns false for shapes / formats it does not take (the caller falls back).
 void launch_x_f16_pairs(void* x16, float* rsc, const void* x, long ldx, int M, int K, hipStream_t s) {
@@ -904,7 +906,7 @@ bool launch_gguf_prefill(int epi, void* out, long ldo, const void* x16, const fl
   // 32-bit buffer offsets inside one x tile
   if ((long)256 * ldx * 2 >= (1L << 31)) return false;  // the largest tile's x rows (qpg: 256)
   for (int i = 0; i < nparts; ++i)
-    if (!qpg_format(parts[i].qtype) || parts[i].rows % 16) return false;  // Q2_K / Q3_K: no block prefill body
+    if (!qpg_format(parts[i].qtype) || parts[i].rows % 16) return false;  // Q2_K / Q3_K / IQ4: no block prefill body
   if (glu && (parts[0].qtype != parts[1].qtype || parts[0].rows != parts[1].rows)) return false;
   int fmts[kMaxParts], nf = 0;
   for (int i = 0; i < nparts; ++i) {

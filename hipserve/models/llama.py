@@ -301,6 +301,11 @@ class LlamaModel(MoEMixin):
                    "gate_exps": 11, "up_exps": 11, "down_exps": 12},
         "q2_k": {"q": 10, "k": 10, "v": 11, "o": 11, "gate": 10, "up": 10, "down": 11, "output": 14,
                  "gate_exps": 10, "up_exps": 10, "down_exps": 11},
+        # the 4-bit codebook formats (23 = IQ4_XS, 20 = IQ4_NL), output in Q6_K as the real mixes roughly are
+        "iq4_xs": {**{n: 23 for n in ("q", "k", "v", "o", "gate", "up", "down", "gate_exps", "up_exps", "down_exps")},
+                   "output": 14},
+        "iq4_nl": {**{n: 20 for n in ("q", "k", "v", "o", "gate", "up", "down", "gate_exps", "up_exps", "down_exps")},
+                   "output": 14},
     }
     # distinct random expert stacks generated on the host per (format, shape); further layers
     # reuse them round-robin (each layer still holds its own device copy)
@@ -335,8 +340,8 @@ class LlamaModel(MoEMixin):
         rng = np.random.default_rng(seed)
 
         def qtype(kind, k, n=16):  # llama.cpp-style fallback when K is not a multiple of the super-block
-            t = types[kind]     # (Q2_K / Q3_K: tiled layout only, so also when N is no multiple of 16)
-            return t if k % G.BLOCK[t][0] == 0 and not (t in (G.Q2_K, G.Q3_K) and n % 16) else G.Q8_0
+            t = types[kind]     # (Q2_K / Q3_K / IQ4: tiled layout only, so also when N % 16 or K % 256)
+            return t if k % G.BLOCK[t][0] == 0 and not (t in Q.TILED_ONLY and (n % 16 or k % 256)) else G.Q8_0
 
         def mat(*specs):  # (kind, N, K) parts stacked along N
             raws = [(qtype(k, kk, n), n, kk, Q.random_blocks(rng, qtype(k, kk, n), n, kk)) for k, n, kk in specs]

@@ -55,14 +55,21 @@ FORMATS = (
     Format("INT4", INT4, 10, 2560, -1, False, False, False, True),
     Format("Q2_K", G.Q2_K, 11, 1344, 8, True, False, False, True),
     Format("Q3_K", G.Q3_K, 12, 1824, 7, True, False, False, True),
+    # (13 stays unassigned: ids are tune-cache keys and the dispatch tests hold 13 unknown)
+    Format("IQ4_NL", G.IQ4_NL, 14, 2304, 2, True, False, False, True),
+    Format("IQ4_XS", G.IQ4_XS, 15, 2208, 2, True, False, False, True),
 )
+# GGUF formats that exist in the tiled (v2) layout only: no v1 row-layout kernel, so a tensor
+# that is not tileable or lies beyond the subnormal-dequant range is held as bf16
+TILED_ONLY = (G.Q2_K, G.Q3_K, G.IQ4_NL, G.IQ4_XS)
 BY_KQT = {f.kqt: f for f in FORMATS}  # kernel format id -> row; below: views of the table
 KERNEL_QT = {f.qtype: f.kqt for f in FORMATS}
 CHUNK_BYTES = {f.qtype: f.chunk_bytes for f in FORMATS}
 # gguf_mfma.hip places each quantised integer at bit SUB_SHIFT of a subnormal f16 and scales it
 # by 2^(24 - SUB_SHIFT) inside the f16 FMA: every block scale must stay below 65504 / 2^(24 -
 # SUB_SHIFT) (|w| up to ~2-4). Weights beyond that (none in practice) run on the v1 kernel;
-# Q2_K / Q3_K (limits 0.9995 / 0.4998) have none: QuantWeight.from_gguf keeps such a weight as bf16.
+# Q2_K / Q3_K (limits 0.9995 / 0.4998) and IQ4_NL / IQ4_XS (the codebook byte + 128 at Q8_0's shift:
+# |d| resp. |d (ls - 32)| < 0.0156) have none: QuantWeight.from_gguf keeps such a weight as bf16.
 SUB_SHIFT = {f.qtype: f.sub_shift for f in FORMATS if f.sub_shift >= 0}
 QPG_KQT = tuple(f.kqt for f in FORMATS if f.prefill)  # the block prefill GEMM (qpg_kernel) takes them
 # every GGUF block format: no resident bf16 shadow by default, expert stacks checked
@@ -145,13 +152,18 @@ def repack_tiled(raw: np.ndarray, qtype: int, N: int, K: int) -> np.ndarray:
         sc = G.q3k_scales(b[..., 96:108].reshape(-1, 12)).view(np.uint8)
         parts = [_lanes(b[..., 32:96].reshape(R, nsb, 16, 4, 1, 16), 1), b[..., 0:32].reshape(R, nsb, 512),
                  sc.reshape(R, nsb, 256), b[..., 108:110].reshape(R, nsb, 32)]
+    elif qtype == G.IQ4_XS:
+        # lane 16 g + c: the qs of sub-blocks 2g, 2g + 1 (Q4_0's lanes); the 6-bit scales unpacked to int8 ls - 32
+        sc = G.iq4xs_scales(b[..., 2:8].reshape(-1, 6)).view(np.uint8)
+        parts = [_lanes(b[..., 8:136].reshape(R, nsb, 16, 4, 2, 16), 2), sc.reshape(R, nsb, 128),
+                 b[..., 0:2].reshape(R, nsb, 32)]
     else:
         blk = b.reshape(R, nsb, 16, per, bb)
         if qtype == G.Q8_0:
             q = blk[..., 2:34].reshape(R, nsb, 16, 4, 4, 16)       # lane g: bytes 64 g + 16 i
             parts = [_lanes(q, 4), blk[..., 0:2].reshape(R, nsb, 256)]
         else:
-            qo = 2 if qtype == G.Q4_0 else 4
+            qo = 4 if qtype == G.Q4_1 else 2                        # Q4_0 / IQ4_NL: d, qs
             q = blk[..., qo:qo + 16].reshape(R, nsb, 16, 4, 2, 16)  # lane g: blocks 2g, 2g+1
             parts = [_lanes(q, 2), blk[..., 0:2].reshape(R, nsb, 256)]
             if qtype == G.Q4_1:
@@ -181,6 +193,8 @@ def sub_scale_ok(raw, qtype: int) -> bool:
             return False  # dmin m is the f16 FMA's addend
     elif qtype == G.Q3_K:
         prod = f16(b[:, 108:110])[:, None] * np.abs(G.q3k_scales(b[:, 96:108]).astype(np.float32))
+    elif qtype == G.IQ4_XS:
+        prod = f16(b[:, 0:2])[:, None] * np.abs(G.iq4xs_scales(b[:, 2:8]).astype(np.float32))
     else:
         prod = f16(b[:, 0:2])[:, None]
     # (no lower bound: a d * sc below the f16 normal range is kept with MORE mantissa
@@ -363,12 +377,12 @@ class QuantWeight:
 
     @staticmethod
     def supported(qtype: int, K: int, N: int | None = None, raw=None) -> bool:
-        """A GGUF tensor of ``qtype`` stays quantised. Q2_K / Q3_K exist in the tiled
-        (v2) layout only: with ``N`` / ``raw`` also N % 16 == 0 and every block scale
-        inside the subnormal-dequant range."""
+        """A GGUF tensor of ``qtype`` stays quantised. Q2_K / Q3_K / IQ4_NL / IQ4_XS exist in
+        the tiled (v2) layout only: with ``N`` / ``raw`` also N % 16 == 0 and every block
+        scale inside the subnormal-dequant range."""
         if qtype not in KERNEL_QT or K % 256:
             return False
-        if qtype in (G.Q2_K, G.Q3_K):
+        if qtype in TILED_ONLY:
             return (N is None or N % 16 == 0) and (raw is None or sub_scale_ok(raw, qtype))
         return True
 
@@ -378,7 +392,7 @@ class QuantWeight:
         for n in names:
             t = gf.tensors[n]
             N, K = t.rows_cols
-            if not cls.supported(t.type, K, N, gf.raw(n) if t.type in (G.Q2_K, G.Q3_K) else None):
+            if not cls.supported(t.type, K, N, gf.raw(n) if t.type in TILED_ONLY else None):
                 return torch.cat([torch.from_numpy(gf.tensor_f32(x)).to(device, torch.bfloat16)
                                   for x in names], 0)
             parts.append(QuantPart.build(gf.raw(n), t.type, N, K, device))
@@ -403,7 +417,10 @@ class QuantWeight:
 
 # synthetic block scales: |w| ~ 0.02 for every format (random-init benchmarks)
 _SYNTH_D = {G.Q4_K: (8e-5, 6e-4), G.Q5_K: (4e-5, 6e-4), G.Q6_K: (1.5e-5, 0.0), G.Q8_0: (2.5e-4, 0.0),
-            G.Q4_0: (4e-3, 0.0), G.Q4_1: (4e-3, -0.03), G.Q2_K: (1.8e-3, 2.7e-3), G.Q3_K: (6.25e-4, 0.0)}
+            G.Q4_0: (4e-3, 0.0), G.Q4_1: (4e-3, -0.03), G.Q2_K: (1.8e-3, 2.7e-3), G.Q3_K: (6.25e-4, 0.0),
+            # mean |kvalues| = 56 (IQ4_XS: times mean |ls - 32| = 16); every code and all 64 sub-block
+            # scales occur in the random bytes, the largest |d (ls - 32)| = 7e-4 inside the 0.0156 range
+            G.IQ4_NL: (3.6e-4, 0.0), G.IQ4_XS: (2.2e-5, 0.0)}
 
 
 def random_blocks(rng: np.random.Generator, qtype: int, N: int, K: int) -> np.ndarray:
@@ -425,7 +442,7 @@ def random_blocks(rng: np.random.Generator, qtype: int, N: int, K: int) -> np.nd
         b[:, :, 82:84] = f16(dm)
     elif qtype == G.Q3_K:
         b[:, :, 108:110] = f16(d)
-    elif qtype in (G.Q8_0, G.Q4_0, G.Q5_0):
+    elif qtype in (G.Q8_0, G.Q4_0, G.Q5_0, G.IQ4_NL, G.IQ4_XS):
         b[:, :, 0:2] = f16(d)
     elif qtype in (G.Q4_1, G.Q5_1):
         b[:, :, 0:2] = f16(d)

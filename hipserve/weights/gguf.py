@@ -10,7 +10,7 @@ Python package is available):
   tensor infos (GGUF v2/v3), ``model_config()`` from ``llama.*`` metadata;
 * block codecs    — numpy reference dequantisers (and quantisers, used to write
   synthetic test/benchmark files) for F32/F16/BF16/Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/
-  Q2_K/Q3_K/Q4_K/Q5_K/Q6_K, bit-exact with ggml's block layouts;
+  Q2_K/Q3_K/Q4_K/Q5_K/Q6_K/IQ4_NL/IQ4_XS, bit-exact with ggml's block layouts;
 * ``GGUFTokenizer`` — SentencePiece-BPE (``llama``) and byte-level BPE (``gpt2``,
   Llama-3) tokenizers built from the embedded vocab;
 * ``load_gguf_weights`` — maps ``blk.N.*`` tensors onto the hipserve model; the
@@ -35,14 +35,17 @@ GGUF_MAGIC = b"GGUF"
 # ggml tensor types (ggml.h)
 F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 0, 1, 2, 3, 6, 7, 8, 9
 Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, Q8_K = 10, 11, 12, 13, 14, 15
+IQ4_NL, IQ4_XS = 20, 23
 BF16 = 30
 TYPE_NAMES = {F32: "F32", F16: "F16", Q4_0: "Q4_0", Q4_1: "Q4_1", Q5_0: "Q5_0", Q5_1: "Q5_1",
               Q8_0: "Q8_0", Q8_1: "Q8_1", Q2_K: "Q2_K", Q3_K: "Q3_K", Q4_K: "Q4_K", Q5_K: "Q5_K",
-              Q6_K: "Q6_K", Q8_K: "Q8_K", BF16: "BF16"}
+              Q6_K: "Q6_K", Q8_K: "Q8_K", IQ4_NL: "IQ4_NL", IQ4_XS: "IQ4_XS", BF16: "BF16"}
 # (block elements, bytes per block)
 BLOCK = {F32: (1, 4), F16: (1, 2), BF16: (1, 2), Q4_0: (32, 18), Q4_1: (32, 20), Q5_0: (32, 22),
          Q5_1: (32, 24), Q8_0: (32, 34), Q2_K: (256, 84), Q3_K: (256, 110), Q4_K: (256, 144),
-         Q5_K: (256, 176), Q6_K: (256, 210)}
+         Q5_K: (256, 176), Q6_K: (256, 210), IQ4_NL: (32, 18), IQ4_XS: (256, 136)}
+# the IQ4_NL / IQ4_XS codebook: a weight is scale * IQ4_VALUES[nibble]
+IQ4_VALUES = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.int8)
 
 # metadata value types
 _U8, _I8, _U16, _I16, _U32, _I32, _F32, _BOOL, _STR, _ARR, _U64, _I64, _F64 = range(13)
@@ -252,6 +255,24 @@ def q3k_scales(scales: np.ndarray) -> np.ndarray:
     return ((lo | (hi << 4)).astype(np.int16) - 32).astype(np.int8)
 
 
+def iq4xs_scales(sc: np.ndarray) -> np.ndarray:
+    """[nb, 6] IQ4_XS scale bytes (u16 scales_h, scales_l[4]) -> the 8 signed sub-block scales
+    ls - 32, int8 [nb, 8]: low 4 bits in the nibbles of scales_l[ib / 2], high 2 bits at bit
+    2 ib of scales_h."""
+    s = sc.astype(np.uint8)
+    ib = np.arange(8)
+    sh = s[:, 0].astype(np.uint16) | (s[:, 1].astype(np.uint16) << 8)
+    lo = (s[:, 2 + ib // 2] >> (4 * (ib % 2)).astype(np.uint8)) & 0xF
+    hi = ((sh[:, None] >> (2 * ib).astype(np.uint16)) & 3).astype(np.uint8)
+    return ((lo | (hi << 4)).astype(np.int16) - 32).astype(np.int8)
+
+
+def _iq4_values(qs: np.ndarray) -> np.ndarray:
+    """[..., 16] qs bytes of 32 weights -> their codebook values, float32 [..., 32]: low nibbles
+    are elements 0-15, high nibbles 16-31 (Q4_0's arrangement)."""
+    return IQ4_VALUES[np.concatenate([qs & 0xF, qs >> 4], axis=-1)].astype(np.float32)
+
+
 def _q23_quants(qs: np.ndarray) -> np.ndarray:
     """[nb, 64] Q2_K / Q3_K qs -> the 2-bit fields in element order [nb, 256]: element
     128 h + 32 j + l sits in bits 2 j .. 2 j + 1 of qs[32 h + l]."""
@@ -347,6 +368,11 @@ def dequantize(raw: np.ndarray, qtype: int, n: int) -> np.ndarray:
         hb = (b[:, 0:32].reshape(nb, 1, 32) >> np.arange(8, dtype=np.uint8).reshape(1, 8, 1)) & 1
         q = (_q23_quants(b[:, 32:96]) | (hb.reshape(nb, 256) << 2)).astype(np.float32) - 4
         return ((d * s)[:, :, None] * q.reshape(nb, 16, 16)).reshape(-1)
+    if qtype == IQ4_NL:  # w = d kvalues[nibble]
+        return (_f16(b[:, 0:2]) * _iq4_values(b[:, 2:18])).reshape(-1)
+    if qtype == IQ4_XS:  # w = d (ls - 32) kvalues[nibble], a 6-bit ls per 32 weights
+        dl = _f16(b[:, 0:2]) * iq4xs_scales(b[:, 2:8]).astype(np.float32)
+        return (dl[:, :, None] * _iq4_values(b[:, 8:136].reshape(nb, 8, 16))).reshape(-1)
     raise NotImplementedError(f"GGUF type {TYPE_NAMES.get(qtype, qtype)} not supported")
 
 
@@ -494,6 +520,31 @@ def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
         hi2 = u >> 4
         out[:, 104:108] = hi2[:, 0:4] | (hi2[:, 4:8] << 2) | (hi2[:, 8:12] << 4) | (hi2[:, 12:16] << 6)
         out[:, 108:110] = _to_f16_bytes(d)
+        return out.reshape(-1)
+    if qtype in (IQ4_NL, IQ4_XS):
+        # nearest codebook entry under an absmax scale per 32 weights (the element of largest
+        # magnitude maps to -127, the long end of the table): not llama.cpp's search. IQ4_XS:
+        # that scale is d (ls - 32), the sub-block scale of largest magnitude landing on -32
+        sub = xb.reshape(nb, be // 32, 32)
+        s = np.take_along_axis(sub, np.abs(sub).argmax(2)[:, :, None], 2)[:, :, 0] / -127.0
+        if qtype == IQ4_NL:
+            eff = s.astype(np.float16).astype(np.float32)
+            out[:, 0:2] = _to_f16_bytes(eff[:, 0])
+        else:
+            smax = np.take_along_axis(s, np.abs(s).argmax(1)[:, None], 1)[:, 0]
+            d = (smax / -32.0).astype(np.float16).astype(np.float32)
+            ls = np.clip(np.round(s / np.where(d != 0, d, 1)[:, None]), -32, 31)
+            eff = d[:, None] * ls
+            u = (ls + 32).astype(np.uint16)                                               # 0..63
+            out[:, 0:2] = _to_f16_bytes(d)
+            out[:, 2:4] = ((u >> 4) << (2 * np.arange(8, dtype=np.uint16))).sum(1, dtype=np.uint16) \
+                .astype("<u2").view(np.uint8).reshape(nb, 2)
+            out[:, 4:8] = ((u[:, 0::2] & 0xF) | ((u[:, 1::2] & 0xF) << 4)).astype(np.uint8)
+        t = sub / np.where(eff != 0, eff, 1)[:, :, None]
+        kv = IQ4_VALUES.astype(np.float32)
+        q = np.searchsorted((kv[:-1] + kv[1:]) / 2, t)  # nearest entry: the interval between midpoints
+        q = np.where(eff[:, :, None] != 0, q, 8).astype(np.uint8)  # an all-zero (sub-)block: the entry nearest 0
+        out[:, bb - be // 2:] = (q[:, :, :16] | (q[:, :, 16:] << 4)).reshape(nb, be // 2)
         return out.reshape(-1)
     raise NotImplementedError(f"quantize to {TYPE_NAMES.get(qtype, qtype)}")
 
@@ -906,25 +957,29 @@ def load_gguf_weights(model, path: str):
         model.layers.append(lw)
     from ..ops.quant import BY_KQT, QuantMoE, quant_linear
 
-    def q23(w):  # a Q2_K / Q3_K projection part or expert stack: resident as tiled blocks only
-        return BY_KQT[w.kqt].qtype in (Q2_K, Q3_K)
     mats = [model.lm_head] + [w for lw in model.layers for w in (lw.wqkv, lw.wo, lw.wgu, lw.wd)]
-    held = [p.nbytes for w in mats if isinstance(w, QuantWeight) for p in w.parts if q23(p)]
-    held += [w.q.numel() for lw in model.layers for w in (lw.w13, lw.w2) if isinstance(w, QuantMoE) and q23(w)]
-    if held:
-        log.info("GGUF %s: %d Q2_K / Q3_K matrices and expert stacks kept as tiled blocks, %.1f MB", path, len(held),
-                 sum(held) / 1e6)
+    # projection parts and expert stacks of the formats that are resident as tiled blocks only
+    for types in ((Q2_K, Q3_K), (IQ4_NL, IQ4_XS)):
+        held = [p.nbytes for w in mats if isinstance(w, QuantWeight) for p in w.parts if BY_KQT[p.kqt].qtype in types]
+        held += [w.q.numel() for lw in model.layers for w in (lw.w13, lw.w2)
+                 if isinstance(w, QuantMoE) and BY_KQT[w.kqt].qtype in types]
+        if held:
+            log.info("GGUF %s: %d %s matrices and expert stacks kept as tiled blocks, %.1f MB", path, len(held),
+                     " / ".join(TYPE_NAMES[t] for t in types), sum(held) / 1e6)
     model.quant_linear = quant_linear
     model.gguf = gf
     return gf
 
 
 def write_synthetic_llama_gguf(path: str, cfg, qtype: int = Q8_0, seed: int = 0, std: float = 0.05,
-                               vocab_tokens: list[str] | None = None, mixed_k: bool = False, embd_type: int = F16):
+                               vocab_tokens: list[str] | None = None, mixed_k: bool = False, embd_type: int = F16,
+                               tensor_types: dict | None = None):
     """Write a random-weight llama GGUF (tests and GGUF-tier benchmarks; no
     network means no real checkpoints). ``mixed_k`` mimics Q4_K_M: attn_v and
     ffn_down in Q6_K, the rest in Q4_K. ``embd_type``: the ggml type of
-    ``token_embd.weight`` (real Q2_K / Q3_K files hold it quantised)."""
+    ``token_embd.weight`` (real Q2_K / Q3_K files hold it quantised). ``tensor_types``:
+    {"q" | "k" | "v" | "o" | "gate" | "up" | "down" | "output": ggml type} overriding single
+    matrices (an IQ4_XS file's Q6_K output and IQ4_NL tensors)."""
     rng = np.random.default_rng(seed)
     H, I, D = cfg.hidden_size, cfg.intermediate_size, cfg.head_dim
     nq, nkv, V = cfg.num_heads, cfg.num_kv_heads, cfg.vocab_size
@@ -946,13 +1001,15 @@ def write_synthetic_llama_gguf(path: str, cfg, qtype: int = Q8_0, seed: int = 0,
           "tokenizer.ggml.bos_token_id": 1, "tokenizer.ggml.eos_token_id": 2}
     k4 = Q4_K if mixed_k else qtype
     k6 = Q6_K if mixed_k else qtype
+    tt = {**{k: k4 for k in ("q", "k", "o", "gate", "up")}, **{k: k6 for k in ("v", "down", "output")},
+          **(tensor_types or {})}
     tensors = [("token_embd.weight", r(V, H), embd_type), ("output_norm.weight", 1 + r(H), F32),
-               ("output.weight", r(V, H), k6)]
+               ("output.weight", r(V, H), tt["output"])]
     for i in range(cfg.num_layers):
         n = gguf_name_map(i)
-        tensors += [(n["attn_norm"], 1 + r(H), F32), (n["q"], r(nq * D, H), k4), (n["k"], r(nkv * D, H), k4),
-                    (n["v"], r(nkv * D, H), k6), (n["o"], r(H, nq * D), k4), (n["ffn_norm"], 1 + r(H), F32),
-                    (n["gate"], r(I, H), k4), (n["up"], r(I, H), k4), (n["down"], r(H, I), k6)]
+        tensors += [(n["attn_norm"], 1 + r(H), F32), (n["q"], r(nq * D, H), tt["q"]), (n["k"], r(nkv * D, H), tt["k"]),
+                    (n["v"], r(nkv * D, H), tt["v"]), (n["o"], r(H, nq * D), tt["o"]), (n["ffn_norm"], 1 + r(H), F32),
+                    (n["gate"], r(I, H), tt["gate"]), (n["up"], r(I, H), tt["up"]), (n["down"], r(H, I), tt["down"])]
     write_gguf(path, md, tensors)
     return path
 

@@ -35,7 +35,8 @@ SHAPES = {  # Q4_K_M: attn_v / ffn_down / output in Q6_K
 }
 
 
-GGUF_KINDS = {"q4_1": G.Q4_1, "q2_k": G.Q2_K, "q3_k": G.Q3_K, "q4_k": G.Q4_K}
+GGUF_KINDS = {"q4_0": G.Q4_0, "q4_1": G.Q4_1, "q2_k": G.Q2_K, "q3_k": G.Q3_K, "q4_k": G.Q4_K, "iq4_nl": G.IQ4_NL,
+              "iq4_xs": G.IQ4_XS}
 
 
 def _time(fn, reps=20, graph_reps=10):
@@ -71,7 +72,8 @@ def main():
     ap.add_argument("--kind", default=None, nargs="+", choices=["int4", "int8"] + sorted(GGUF_KINDS),
                     help="every part of the same shapes in ONE format: int4 (group 128, asymmetric: the AWQ / "
                          "compressed-tensors W4A16 layout), int8 (group 128) or GGUF blocks of one type (q4_1: "
-                         "INT4's 2,560-byte chunk; q2_k / q3_k next to q4_k: the same shapes in one run). "
+                         "INT4's 2,560-byte chunk; q2_k / q3_k / iq4_xs / iq4_nl next to q4_k / q4_0: the same shapes "
+                         "in one run). "
                          "Several kinds run one after the other per projection")
     ap.add_argument("--prefill", action="store_true",
                     help="M > 64: the prefill GEMM from the blocks (qpf) and the M-tiled dequant-MFMA kernel vs "

@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--output-len", type=int, default=256)
     ap.add_argument("--block-size", type=int, default=16)
     ap.add_argument("--decode-partition", type=int, default=512)
+    ap.add_argument("--quantization", default=None, help="synthetic quantised weights (the server's --quantization)")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -40,7 +41,8 @@ def main():
 
     eng = LLMEngine(EngineConfig(model=a.model, load_format="dummy", device="cuda", max_num_seqs=a.concurrency,
                                  max_num_batched_tokens=8192, max_model_len=a.input_len + a.output_len + 16,
-                                 block_size=a.block_size, decode_partition=a.decode_partition),
+                                 block_size=a.block_size, decode_partition=a.decode_partition,
+                                 extra={"quantization": a.quantization} if a.quantization else {}),
                     tp=TPGroup(0, 1, None, torch.device("cuda", 0)))
     rng = np.random.default_rng(0)
     sp = SamplingParams(temperature=0.8, top_p=0.95, max_tokens=a.output_len, ignore_eos=True)
