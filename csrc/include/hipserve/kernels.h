@@ -245,6 +245,23 @@ bool launch_prefill_gemm_f8(int epi, void* C, long ldc, const void* A, long lda,
 // ws[S, M, N] = (xq . wq^T over K slice s) * xs[m] * rs[n] / 256; (K / 256) / S in
 // {1, 2, 3, 4, 6, 7, 8, 12, 14, 16, 21}; part rows % 16 == 0. W.xs = xs.
 bool launch_fp8_decode_gemm(float* ws, const void* xq, const PgF8& W, int M, int N, int K, int S, hipStream_t s);
+// MXFP4 W4A8 GEMM (mxfp4.hip), M <= 256: fp32 split-K partials ws[S, M, N] = (xq . w^T
+// over K slice s) * xs[m], w = e2m1 * 2^(E8M0 - 127) per 32 k in 2,176-byte chunks per
+// 16 rows x 256 k (ops/quant.py QuantPart.from_mxfp4), up to 4 parts stacked along N
+// (rows % 16 == 0, summing to N); (K / 256) / S in fp8_decode.hip's step set.
+constexpr int kPgMxParts = 4;
+struct PgMxPart {
+  const unsigned char* q;
+  int rows;
+};
+struct PgMx {
+  PgMxPart p[kPgMxParts];
+  int n;
+  const float* xs;
+};
+bool launch_mxfp4_gemm(float* ws, const void* xq, const PgMx& W, int M, int N, int K, int S, hipStream_t s);
+// one tiled MXFP4 part -> bf16 [N, K] rows of stride ldo (% 8) elements, exact
+bool launch_mxfp4_dequant(void* out, long ldo, const void* q, int N, int K, hipStream_t s);
 // act = silu / gelu_tanh(gate) * up of [gate | up] rows, written as per-token e4m3 q8 [rows,
 // inter] + xs [rows] (and bf16 into out if non-null); inter / 8 <= 4096. activation.hip
 bool launch_glu_quant(bool gelu, void* out, void* q8, float* xs, const void* in, long rows, int inter,

@@ -1155,6 +1155,49 @@ void fp8_decode_gemm(at::Tensor& ws, const at::Tensor& xq, const at::Tensor& xs,
               "fp8_decode_gemm: unsupported (M <= 256, part rows % 16, (K / 256) / splits in the kernel's step set)");
 }
 
+// MXFP4 W4A8 (mxfp4.hip): fp32 split-K partials ws [S, M, N] of the per-token e4m3
+// activations xq / xs against tiled MXFP4 parts (ops/quant.py QuantPart.from_mxfp4:
+// q [rows/16, K/256, 2176] uint8) of ``rows`` rows each, stacked along N.
+void mxfp4_gemm(at::Tensor& ws, const at::Tensor& xq, const at::Tensor& xs, const std::vector<at::Tensor>& q,
+                const std::vector<int64_t>& rows, int64_t splits) {
+  Args a("mxfp4_gemm", xq, "xq");
+  const void* xp = a.ptr(xq, "xq", U8, CONTIG, {at_least(1), at_least(256)});
+  const int M = xq.size(0), K = xq.size(1);
+  TORCH_CHECK(K % 256 == 0 && splits >= 1, "mxfp4_gemm: K % 256 == 0, splits >= 1");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(xp) % 16 == 0, "mxfp4_gemm: xq must be 16-byte aligned");
+  TORCH_CHECK(!q.empty() && q.size() <= (size_t)hipserve::kPgMxParts && rows.size() == q.size(), "mxfp4_gemm: 1-",
+              hipserve::kPgMxParts, " parts of q and rows");
+  hipserve::PgMx W{};
+  W.n = (int)q.size();
+  W.xs = a.as<float>(xs, "xs", CONTIG, exactly(M));
+  int64_t N = 0;
+  for (size_t i = 0; i < q.size(); ++i) {
+    TORCH_CHECK(rows[i] >= 16 && rows[i] % 16 == 0, "mxfp4_gemm: rows[i] must be a positive multiple of 16");
+    const uint8_t* qp = a.as<uint8_t>(q[i], "q[i] (tiled MXFP4 [rows/16, K/256, 2176])", CONTIG,
+                                      exactly(rows[i] / 16 * (K / 256) * 2176));
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(qp) % 16 == 0, "mxfp4_gemm: q[i] must be 16-byte aligned");
+    W.p[i] = hipserve::PgMxPart{qp, (int)rows[i]};
+    N += rows[i];
+  }
+  TORCH_CHECK(N < (1 << 24), "mxfp4_gemm: rows sum below 2^24");
+  float* wsp = splitk_ws(a, ws, splits, M, N);
+  TORCH_CHECK(hipserve::launch_mxfp4_gemm(wsp, xp, W, M, (int)N, K, (int)splits, cur_stream()),
+              "mxfp4_gemm: unsupported (M <= 256, (K / 256) / splits in the kernel's step set)");
+}
+
+// one tiled MXFP4 part q [N/16, K/256, 2176] -> out bf16 [N, K] (rows 16-byte aligned), exact
+void mxfp4_dequant(at::Tensor& out, const at::Tensor& q, int64_t N, int64_t K) {
+  Args a("mxfp4_dequant", q, "q");
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && K >= 256 && K % 256 == 0 && N < (1 << 24) && K < (1 << 24),
+              "mxfp4_dequant: N % 16 == 0, K % 256 == 0");
+  const void* qp = a.ptr(q, "q (a tiled MXFP4 part of N x K)", U8, CONTIG, exactly(N / 16 * (K / 256) * 2176));
+  void* op = a.ptr(out, "out", BF16, ROWS8, {N, K});
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(op) % 16 == 0 && reinterpret_cast<uintptr_t>(qp) % 16 == 0,
+              "mxfp4_dequant: out and q must be 16-byte aligned");
+  TORCH_CHECK(hipserve::launch_mxfp4_dequant(op, out.stride(0), qp, (int)N, (int)K, cur_stream()),
+              "mxfp4_dequant: unsupported shape");
+}
+
 // [gate | up] rows -> per-token e4m3 act (q8 [rows, I] uint8, xs [rows] fp32), optionally
 // the bf16 act too: glu_and_mul -> act_quant_fp8 in one pass
 void glu_quant(const c10::optional<at::Tensor>& out, at::Tensor& q8, at::Tensor& xs, const at::Tensor& x, bool gelu) {
@@ -1566,6 +1609,8 @@ TORCH_LIBRARY(hipserve, m) {
   m.def("gguf_dequant_tiled(Tensor(a!) out, Tensor q, Tensor rs, int qtype, int N, int K, int pack=0, int nrows=0, bool kmajor=False) -> ()",
         &gguf_dequant_tiled);
   m.def("fp8_untile(Tensor(a!) out, Tensor q, int N, int K) -> ()", &fp8_untile);
+  m.def("mxfp4_gemm(Tensor(a!) ws, Tensor xq, Tensor xs, Tensor[] q, int[] rows, int splits) -> ()", &mxfp4_gemm);
+  m.def("mxfp4_dequant(Tensor(a!) out, Tensor q, int N, int K) -> ()", &mxfp4_dequant);
   m.def("quant_formats() -> str", &quant_formats);
   m.def("qmoe_gemm(Tensor(a!) out, Tensor(b!) ws, Tensor x, Tensor q, Tensor rs, int qtype, int N, int K, Tensor slots, Tensor tile_expert, int tile, int gather_k, int splits, bool kmajor=False, int glu=0) -> int", &qmoe_gemm);
   m.def("lora_shrink_splits(int M, int K) -> int", &lora_shrink_splits);

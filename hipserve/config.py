@@ -597,10 +597,24 @@ def default_batched_tokens(model: str, load_format: str = "auto", quantization: 
     7,607 / 432 ms (profiles/r5_bench_8b_chunk16k.json, r5_bench_8b_chunk4k.json)."""
     if quantization is None:
         quantization = checkpoint_quantization(model)
-    if quantization in ("int8", "int4"):  # int4: the explicit flag only (checkpoint_quantization
-        return 32768                      # reports no 4-bit kind: auto-detected ones keep 8192, unmeasured)
+    if quantization in ("int8", "int4", "mxfp4"):  # int4: the explicit flag only (checkpoint_quantization
+        return 32768  # reports no 4-bit integer kind: auto-detected ones keep 8192, unmeasured); mxfp4
+        # dequantises per prefill step like INT8 and takes its budget (not measured)
     gguf = quantization in GGUF_QUANTS or load_format == "gguf" or str(model).lower().endswith(".gguf")
     return 16384 if gguf else 8192
+
+
+def quark_mxfp4(q: dict) -> bool:
+    """``quantization_config`` of an AMD Quark MXFP4 checkpoint: quant_method "quark" whose
+    weight spec (global, or the first layer-wise one) is fp4 in groups of 32 with E8M0 scales."""
+    if str(q.get("quant_method", "")).lower() != "quark":
+        return False
+    g = q.get("global_quant_config") or {}
+    w = g.get("weight") or next(iter((q.get("layer_quant_config") or {}).values()), {}).get("weight") or {}
+    if isinstance(w, list):
+        w = w[0] if w else {}
+    return (str(w.get("dtype", "")).lower() == "fp4" and int(w.get("group_size", 0) or 0) == 32
+            and str(w.get("scale_format", "")).lower() == "e8m0")
 
 
 def checkpoint_quantization(model: str) -> str | None:
@@ -618,6 +632,8 @@ def checkpoint_quantization(model: str) -> str | None:
     method = str(q.get("quant_method", "")).lower()
     if method == "fp8":
         return "fp8"
+    if quark_mxfp4(q):
+        return "mxfp4"
     if method in ("awq", "gptq"):
         return "int8" if int(q.get("bits", 0)) == 8 else None
     for grp in (q.get("config_groups") or {}).values():

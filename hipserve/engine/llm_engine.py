@@ -42,7 +42,7 @@ def prepare_model(cfg: EngineConfig, tp: TPGroup, model_cfg: ModelConfig | None 
         cfg = cfg.replace(model=path, served_model_name=cfg.served_model_name or cfg.model,
                           tokenizer=cfg.tokenizer if cfg.tokenizer and cfg.tokenizer != cfg.model else None)
     mcfg = model_cfg or resolve_model_config(cfg.model, cfg.served_model_name)
-    if cfg.extra.get("quantization") and cfg.extra["quantization"] not in ("fp8", "int8", "int4") and cfg.load_format == "dummy":
+    if cfg.extra.get("quantization") and cfg.extra["quantization"] not in ("fp8", "int8", "int4", "mxfp4") and cfg.load_format == "dummy":
         # synthetic GGUF tier: ggml llama weights use interleaved-pair RoPE
         mcfg = mcfg.replace(rope_mode=1)
     tokenizer = get_tokenizer(cfg.model, mcfg, cfg.tokenizer)
@@ -55,6 +55,10 @@ class LLMEngine:
     def __init__(self, cfg: EngineConfig, tp: TPGroup | None = None,
                  model_cfg: ModelConfig | None = None):
         self.tp = tp or get_tp()
+        if self.tp.world_size > 1 and cfg.extra.get("quantization") == "mxfp4":
+            from ..ops.quant import MXFP4_TP_ERROR
+
+            raise ValueError(MXFP4_TP_ERROR)  # (a checkpoint's MXFP4 is refused by its loader)
         self.cfg, self.model_cfg, self.tokenizer = prepare_model(cfg, self.tp, model_cfg)
         cfg = self.cfg
         vcfg = self.model_cfg.vision

@@ -329,7 +329,7 @@ class LlamaModel(MoEMixin):
 
         from ..weights import gguf as G
 
-        if scheme.lower() in ("fp8", "int8", "int4"):
+        if scheme.lower() in ("fp8", "int8", "int4", "mxfp4"):
             return self.allocate_random_fp8(seed, scheme.lower())
         if self.tp.world_size != 1:
             raise NotImplementedError("the GGUF tier runs TP=1 (one device per pod, like llama-server)")
@@ -415,6 +415,8 @@ class LlamaModel(MoEMixin):
         the quantised expert GEMM. Embeddings, norms, router and lm_head stay bf16 (the
         checkpoints' ``ignore`` list). Off the GPU the same 8-bit values are
         dequantised to dense weights."""
+        if kind == "mxfp4" and self.tp.world_size != 1:
+            raise ValueError(Q.MXFP4_TP_ERROR)
         self.allocate_random(seed=seed)  # norms, embeddings, lm_head, bf16 projections (replaced below)
         dev = self.device
 
@@ -423,6 +425,19 @@ class LlamaModel(MoEMixin):
             # expert w2 at TP > 1) takes the max over the ranks' K slices, so every TP
             # degree quantises the same model as TP = 1 (a sharded checkpoint's scale)
             wf = w.float()
+            if kind == "mxfp4":
+                N, K = wf.shape
+                if K % 32:
+                    return None, w
+                # MXFP4 (dense projections only): the uniform weights of allocate_random -> uniform
+                # codes, all 16 occurring; a block's E8M0 byte is 119..121 by its first code
+                # (mean |e2m1| 2.25 x mean scale 2^-7 x 7/6: |w| ~ 0.02)
+                u = torch.round((wf / (0.02 * math.sqrt(3.0)) + 1.0) * 7.5).clamp_(0, 15).to(torch.uint8)
+                nib = u[:, 0::2] | (u[:, 1::2] << 4)
+                sc = 119 + u[:, ::32] % 3
+                ok = dev.type == "cuda" and N % 16 == 0 and K % 256 == 0
+                return ((Q.QuantPart.from_mxfp4(nib, sc, dev) if ok else None),
+                        Q.mxfp4_dequantize(nib, sc).to(device=dev, dtype=self.dtype))
             if kind == "int4":
                 N, K = wf.shape
                 G = 128 if K % 128 == 0 else 32 if K % 32 == 0 else K
@@ -981,6 +996,8 @@ class LlamaModel(MoEMixin):
             fc = gemm.fused_choice(x.shape[0], w)
             return gemm.gemm_partial(x, w, fc) if fc is not None else None
         M = x.shape[0]
+        if Q.is_mxfp4(w):  # MXFP4 W4A8 (mxfp4.hip): up to 256 rows, TP = 1 only (refused at load)
+            return Q.quant_partial(x, w, x16, x8) if x.is_cuda and M <= Q.F8_DECODE_MAX_M else None
         # FP8 W8A8 above 64 rows: TP = 1 (the cross-rank epilogues are sized for <= 64 rows)
         if getattr(w, "v2", False) and x.is_cuda and (M <= Q.MAX_FUSED_M or (
                 M <= Q.F8_DECODE_MAX_M and self.tp.world_size == 1 and Q.f8_decode_ok(w))):

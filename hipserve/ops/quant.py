@@ -62,6 +62,13 @@ FORMATS = (
 # GGUF formats that exist in the tiled (v2) layout only: no v1 row-layout kernel, so a tensor
 # that is not tileable or lies beyond the subnormal-dequant range is held as bf16
 TILED_ONLY = (G.Q2_K, G.Q3_K, G.IQ4_NL, G.IQ4_XS)
+# OCP MXFP4 (e2m1 elements, one E8M0 scale byte per 32 k): NOT a row of the table — it has
+# kernels of its own (csrc/kernels/mxfp4.hip: the scaled FP4 MFMA against e4m3 activations,
+# no dequant-MFMA body), so no gguf_mfma.hip body or guard. Its id 16 only keys signatures
+# and the tune cache.
+MXFP4, MXFP4_KQT, MXFP4_CHUNK = 1005, 16, 2176
+MXFP4_TP_ERROR = ("MXFP4 weights run on one device only (tensor_parallel_size 1): the W4A8 GEMM has no "
+                  "cross-rank epilogue, and dequantising every projection per decode step is no substitute")
 BY_KQT = {f.kqt: f for f in FORMATS}  # kernel format id -> row; below: views of the table
 KERNEL_QT = {f.qtype: f.kqt for f in FORMATS}
 CHUNK_BYTES = {f.qtype: f.chunk_bytes for f in FORMATS}
@@ -206,6 +213,40 @@ def tileable(N: int, K: int) -> bool:
     return N % 16 == 0 and K % 256 == 0
 
 
+# ---- OCP MXFP4 codec (CPU, torch). Code = sign << 3 | magnitude index into E2M1; two
+# codes per byte, even k in the low nibble (the float4_e2m1fn_x2 order of checkpoints).
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mxfp4_dequantize(nibbles: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """(uint8 [N, K/2], E8M0 uint8 [N, K/32]) -> fp32 [N, K], exact:
+    w[n, k] = e2m1(code) * 2^(scales[n, k / 32] - 127)."""
+    nib = nibbles.to(torch.int64)
+    codes = torch.stack([nib & 15, nib >> 4], -1).reshape(nib.shape[0], -1)
+    val = torch.tensor(E2M1, dtype=torch.float32, device=nib.device)[codes & 7]
+    val = torch.where(codes >= 8, -val, val)
+    sc = torch.ldexp(torch.ones((), dtype=torch.float32, device=nib.device), scales.to(torch.int32) - 127)
+    return val * sc.repeat_interleave(32, 1)
+
+
+def mxfp4_quantize(w: torch.Tensor):
+    """fp [N, K] (K % 32 == 0) -> (nibbles uint8 [N, K/2], scales uint8 [N, K/32]): per
+    32-block the OCP scale exponent floor(log2(amax)) - 2 (e2m1's largest exponent),
+    elements rounded to the nearest e2m1 value, ties to the even mantissa, saturating at 6."""
+    N, K = w.shape
+    if K % 32:
+        raise ValueError(f"mxfp4_quantize: K = {K} is not a multiple of 32")
+    wf = w.detach().to("cpu", torch.float32).reshape(N, K // 32, 32)
+    amax = wf.abs().amax(-1)
+    ex = torch.frexp(amax)[1] - 1                        # floor(log2(amax)) for amax > 0
+    e = torch.where(amax > 0, ex - 2 + 127, torch.zeros_like(ex)).clamp(0, 254)
+    a = torch.ldexp(wf.abs(), (127 - e).unsqueeze(-1))   # |w| / 2^(e - 127), exact
+    # midpoints of neighbouring values; a tie goes down where the lower code is even
+    code = ((a > 0.25).long() + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    code = (code | (torch.signbit(wf).long() << 3)).reshape(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8), e.to(torch.uint8)
+
+
 class QuantPart:
     """One quantised matrix on the device: ``tiled`` parts (N % 16 == 0) hold the v2
     layout in ``q`` [N/16, K/256, chunk]; others (GGUF only) the v1 row layout + SoA
@@ -214,7 +255,7 @@ class QuantPart:
 
     def __init__(self, qtype, N, K, q, d, m, row_bytes, tiled=False, rs=None, sub_ok=True):
         self.qtype, self.N, self.K = qtype, N, K
-        self.kqt = KERNEL_QT[qtype]
+        self.kqt = MXFP4_KQT if qtype == MXFP4 else KERNEL_QT[qtype]
         self.q, self.d, self.m, self.row_bytes = q, d, m, row_bytes
         self.tiled = tiled
         self.sub_ok = sub_ok  # block scales in the v2 kernel's subnormal-dequant range
@@ -312,6 +353,32 @@ class QuantPart:
         return cls(FP8B, N, K, chunk, _E16(device), _E16(device), 0, tiled=True, rs=rs)
 
     @classmethod
+    def from_mxfp4(cls, nibbles: torch.Tensor, scales: torch.Tensor, device):
+        """OCP MXFP4 weight: ``nibbles`` uint8 [N, K/2] (even k in the low nibble),
+        ``scales`` E8M0 uint8 [N, K/32]. N % 16 == 0, K % 256 == 0. One 2,176-byte chunk
+        per 16 rows x 256 k (4.25 bits per weight), laid out for mxfp4.hip:
+          * bytes 0..2047: the 16-byte piece (row c, 32-block b = 4 h + g of the chunk) at
+            h * 1024 + (16 g + c) * 16, its bytes in checkpoint order. The MFMA's fp4
+            operand takes element i of a lane's 32 k from nibble i, low nibble first —
+            byte j = (k 2j, k 2j + 1) — so a piece is the lane's operand as it is, and
+            the 64 lanes' load of one h covers 1 KiB contiguous;
+          * bytes 2048..2175: E8M0 of (row c, block 4 h + g) at 2048 + (16 g + c) * 2 + h:
+            one 2-byte load per lane, 128 B contiguous per wave; byte h is the scale of
+            the lane's MFMA on 128-k tile h (opsel h)."""
+        N, K = nibbles.shape[0], nibbles.shape[1] * 2
+        if nibbles.dim() != 2 or N % 16 or K % 256 or N == 0 or K == 0:
+            raise ValueError(f"mxfp4 weight [{N}, {K}] not supported (needs N % 16 == 0 and K % 256 == 0)")
+        if tuple(scales.shape) != (N, K // 32):
+            raise ValueError(f"mxfp4 scales {tuple(scales.shape)} do not match [{N}, {K // 32}]")
+        if nibbles.dtype != torch.uint8 or scales.dtype != torch.uint8:
+            raise ValueError("mxfp4 nibbles and scales must be uint8")
+        R, nsb = N // 16, K // 256
+        nib = nibbles.to(device).reshape(R, 16, nsb, 2, 4, 16).permute(0, 2, 3, 4, 1, 5).reshape(R, nsb, 2048)
+        sc = scales.to(device).reshape(R, 16, nsb, 2, 4).permute(0, 2, 4, 1, 3).reshape(R, nsb, 128)
+        chunk = torch.cat([nib, sc], 2).contiguous()
+        return cls(MXFP4, N, K, chunk, _E16(device), _E16(device), 0, tiled=True)
+
+    @classmethod
     def build(cls, raw, qtype: int, N: int, K: int, device):
         def to(a, dt):
             return torch.from_numpy(np.array(a, copy=True, order='C')).view(dt).to(device)
@@ -333,6 +400,8 @@ class QuantWeight:
         self.N = sum(p.N for p in parts)
         self.K = parts[0].K
         assert all(p.K == self.K for p in parts)
+        if any(p.qtype == MXFP4 for p in parts) and not all(p.qtype == MXFP4 for p in parts):
+            raise ValueError("MXFP4 parts do not mix with other formats in one projection")
         self._gkey = None
         self.dense = None  # bf16 [N, K] copy for prefill GEMMs (make_dense_shadows), or None
 
@@ -350,7 +419,7 @@ class QuantWeight:
                 cols.append(off)
                 off += p.N
             self._groups = [(kqt, ps, cols) for kqt, (ps, cols) in groups.items()]
-            self._v2 = all(p.tiled and p.sub_ok for p in self.parts)
+            self._v2 = all(p.tiled and p.sub_ok and p.qtype != MXFP4 for p in self.parts)
             cols = np.cumsum([0] + [p.N for p in self.parts])[:-1].tolist()
             self.v2_args = ([p.q for p in self.parts], [p.rs for p in self.parts], [p.kqt for p in self.parts],
                             [p.N for p in self.parts], cols)
@@ -462,7 +531,9 @@ def _dequant_scratch(device, numel):
 
 
 def _dequant_into(buf: torch.Tensor, p: QuantPart):
-    if p.tiled:
+    if p.qtype == MXFP4:
+        torch.ops.hipserve.mxfp4_dequant(buf, p.q, p.N, p.K)
+    elif p.tiled:
         torch.ops.hipserve.gguf_dequant_tiled(buf, p.q, p.rs, p.kqt, p.N, p.K)
     else:
         torch.ops.hipserve.gguf_dequant(buf, p.q, p.d, p.m, p.kqt, p.row_bytes, p.N, p.K)
@@ -589,15 +660,15 @@ def tune_splits(weights, device, ms=M_BUCKETS, max_ws_bytes: int = 256 << 20, f8
 
     seen, report = {}, []
     for w in weights:
-        if isinstance(w, QuantWeight) and w.v2:
+        if isinstance(w, QuantWeight) and (w.v2 or is_mxfp4(w)):
             seen.setdefault(_sig(w), w)
     for sig in list(seen):  # timed by a previous start on this device and kernel build
-        kind = "f8_splits" if f8_decode_ok(seen[sig]) else "gguf_splits"
-        mlist = f8_ms if kind == "f8_splits" else ms
+        kind = _f8_kind(seen[sig]) if f8_decode_ok(seen[sig]) else "gguf_splits"
+        mlist = f8_ms if kind != "gguf_splits" else ms
         hits = [TC.get(device, kind, [list(map(list, sig[1])), sig[0], M]) for M in mlist]
         if all(h is not None for h in hits):
             for M, h in zip(mlist, hits):
-                (F8_SPLIT_TABLE if kind == "f8_splits" else SPLIT_TABLE)[(sig, _bucket(M))] = h["S"]
+                (F8_SPLIT_TABLE if kind != "gguf_splits" else SPLIT_TABLE)[(sig, _bucket(M))] = h["S"]
                 report.append(dict(h["row"], cached=True))
             del seen[sig]
     nbuf = max((4 * w.N * max(f8_ms if f8_decode_ok(w) else ms) * 32 for w in seen.values()), default=0)
@@ -647,11 +718,36 @@ F8D_STEPS = (1, 2, 3, 4, 6, 7, 8, 12, 14, 16, 21)  # (K / 256) / S the kernel is
 F8D_MIN_WGS = 160  # untuned default; measured at 64 rows, 170-250 workgroups of 8 waves stream best
 
 
+def is_mxfp4(w) -> bool:
+    """``w`` is a QuantWeight of MXFP4 parts (never mixed with other formats)."""
+    parts = getattr(w, "parts", None)
+    return bool(parts) and parts[0].qtype == MXFP4
+
+
+def _f8_kind(w) -> str:
+    """Tune-cache key of a weight on the e4m3-activation decode GEMMs."""
+    return "mxfp4_splits" if is_mxfp4(w) else "f8_splits"
+
+
+def _f8_launch(ws, xq, xs, w, S: int):
+    """The W8A8 FP8 or W4A8 MXFP4 decode GEMM of ``w`` with S K slices."""
+    if is_mxfp4(w):
+        torch.ops.hipserve.mxfp4_gemm(ws, xq, xs, [p.q for p in w.parts], [p.N for p in w.parts], S)
+    else:
+        torch.ops.hipserve.fp8_decode_gemm(ws, xq, xs, [p.q for p in w.parts], [p.rs for p in w.parts], S)
+
+
 def f8_decode_ok(w) -> bool:
     """The FP8 decode GEMM takes ``w``: per-channel FP8 parts only (no 128-block
     scales), tiled, at most 4 parts, and a K whose 256-k steps split into a built
-    step count."""
+    step count. Also true for an MXFP4 weight of at most 4 parts: mxfp4_gemm (mxfp4.hip)
+    takes the same e4m3 activations and serves the same rows (any K / 256 splits into
+    one-step slices)."""
     parts = getattr(w, "parts", None)
+    if is_mxfp4(w):
+        if not hasattr(torch.ops.hipserve, "mxfp4_gemm"):
+            raise RuntimeError("MXFP4 weights need the mxfp4_gemm kernel (csrc/kernels/mxfp4.hip): rebuild")
+        return len(parts) <= 4 and parts[0].q.is_cuda
     if not (F8_DECODE and parts and len(parts) <= 4 and hasattr(torch.ops.hipserve, "fp8_decode_gemm")):
         return False
     if not all(p.qtype == FP8 and p.tiled and p.N % 16 == 0 for p in parts) or w.K % 256:
@@ -693,7 +789,7 @@ def f8_decode_partial(x: torch.Tensor, w: QuantWeight, x8=None):
     xq, xs = x8 if x8 is not None else pgemm.act_quant(x)
     S = f8_decode_splits(w, M)
     ws = torch.empty(S * M * w.N, dtype=torch.float32, device=x.device)
-    torch.ops.hipserve.fp8_decode_gemm(ws, xq, xs, [p.q for p in w.parts], [p.rs for p in w.parts], S)
+    _f8_launch(ws, xq, xs, w, S)
     return ws, S
 
 
@@ -705,21 +801,20 @@ def _tune_f8_decode(w, ms, ws) -> list:
     for M in ms:
         x = torch.randn(M, w.K, device=ws.device, dtype=torch.bfloat16)
         xq, xs = pgemm.act_quant(x)
-        qs, rs = [p.q for p in w.parts], [p.rs for p in w.parts]
         cost = {}
         for S in _f8_valid_splits(w):
             if S * M * w.N > ws.numel():
                 continue
-            t = _graph_time_us(lambda S=S: torch.ops.hipserve.fp8_decode_gemm(ws, xq, xs, qs, rs, S))
+            t = _graph_time_us(lambda S=S: _f8_launch(ws, xq, xs, w, S))
             cost[S] = t + 1e6 * S * M * w.N * 4 / PARTIAL_READ_BPS
         if cost:
             best = min(cost, key=cost.get)
             F8_SPLIT_TABLE[(_sig(w), _bucket(M))] = best
-            row = {"K": w.K, "N": w.N, "M": M, "S": best, "kernel": "fp8_w8a8",
+            row = {"K": w.K, "N": w.N, "M": M, "S": best, "kernel": "mxfp4_w4a8" if is_mxfp4(w) else "fp8_w8a8",
                    "us": {k: round(v, 2) for k, v in sorted(cost.items())}}
             rows.append(row)
             from . import tune_cache as TC
-            TC.put(ws.device, "f8_splits", [list(map(list, _sig(w)[1])), w.K, M], {"S": best, "row": row})
+            TC.put(ws.device, _f8_kind(w), [list(map(list, _sig(w)[1])), w.K, M], {"S": best, "row": row})
     return rows
 
 

@@ -11,6 +11,7 @@ network is reachable.
 """
 from __future__ import annotations
 
+import fnmatch
 import json
 import logging
 import os
@@ -68,8 +69,34 @@ class _Ckpt:
                 if k.endswith(suf) and k[: -len(suf)] + ".weight" not in self.where:
                     self.virtual[k[: -len(suf)] + ".weight"] = (kind, k[: -len(suf)])
 
+        # AMD Quark MXFP4: "<x>.weight" uint8 [N, K/2] (two e2m1 codes per byte, even k low)
+        # + "<x>.weight_scale" E8M0 uint8 [N, K/32]; modules on the config's exclude list
+        # (lm_head, ...) are stored as plain bf16
+        from ..config import quark_mxfp4
+
+        self.mxfp4 = quark_mxfp4(self.qcfg)
+        self.exclude = [str(e) for e in (self.qcfg.get("exclude") or [])]
+
     def has(self, name):
         return name in self.where or name in self.virtual
+
+    def is_mxfp4(self, name) -> bool:
+        if not (self.mxfp4 and name.endswith(".weight") and name in self.where and name + "_scale" in self.where):
+            return False
+        mod = name[: -len(".weight")]
+        if any(mod == e or mod.endswith("." + e) or fnmatch.fnmatchcase(mod, e) for e in self.exclude):
+            return False
+        return all(self.where[n].get_slice(n).get_dtype() == "U8" for n in (name, name + "_scale"))
+
+    def mxfp4_part(self, name, axis: int, start: int, stop: int):
+        """(nibbles uint8 [rows, cols / 2], E8M0 scales uint8 [rows, cols / 32]) of rows /
+        columns [start, stop); None when a column slice would split a 32-block."""
+        nib, sc = self._get(name), self._get(name + "_scale")
+        if axis == 0:
+            return nib[start:stop].contiguous(), sc[start:stop].contiguous()
+        if start % 32 or stop % 32:
+            return None
+        return nib[:, start // 2:stop // 2].contiguous(), sc[:, start // 32:stop // 32].contiguous()
 
     def find(self, suffix) -> str | None:
         for k in list(self.where) + list(self.virtual):
@@ -84,6 +111,10 @@ class _Ckpt:
         if name in self.virtual:
             return self._dequant_int(name)
         t = self.where[name].get_tensor(name)
+        if self.is_mxfp4(name):  # exact in bf16 (one mantissa bit x a power of two)
+            from ..ops.quant import mxfp4_dequantize
+
+            return mxfp4_dequantize(t, self._get(name + "_scale")).to(torch.bfloat16)
         return self._dequant(name, t) if t.dtype in _FP8 else t
 
     def rows(self, name, start, stop) -> torch.Tensor:
@@ -210,7 +241,7 @@ class _Ckpt:
 
     def _is_fp8(self, name) -> bool:
         """True for every tensor that must be dequantised whole before slicing."""
-        if name in self.virtual:
+        if name in self.virtual or self.is_mxfp4(name):
             return True
         return self.where[name].get_slice(name).get_dtype() in ("F8_E4M3", "F8_E5M2")
 
@@ -304,9 +335,28 @@ def load_hf_weights(model: LlamaModel, model_path: str):
     native_int4 = native_fp8 and INT4_NATIVE
     n_fp8 = [0]
     n_int4 = [0, 0, 0]  # projections, expert stacks, resident bytes
+    n_mx = [0, 0, 0, 0]  # MXFP4: projections kept, their bytes, projections held as bf16, their bytes
+    if ck.mxfp4 and W > 1:
+        raise ValueError(Q.MXFP4_TP_ERROR)
 
     def proj(specs):
         """specs: [(name, axis, start, stop)] stacked along the output rows."""
+        if ck.mxfp4 and all(ck.is_mxfp4(n) for n, *_ in specs):
+            # Quark MXFP4 (dense q / k / v / o / gate / up / down): the 4-bit chunks on the GPU;
+            # off it, or when a part fails N % 16 / K % 256, this projection alone is bf16
+            parts = [ck.mxfp4_part(n, ax, a, b) for n, ax, a, b in specs] if native_fp8 else None
+            if parts and all(pp is not None and pp[0].shape[0] % 16 == 0 and pp[0].shape[1] % 128 == 0
+                             for pp in parts):
+                w = Q.QuantWeight([Q.QuantPart.from_mxfp4(nib, sc, dev) for nib, sc in parts])
+                n_fp8[0] += 1
+                n_mx[0] += 1
+                n_mx[1] += w.nbytes
+                return w
+            ts = [ck.rows(n, a, b) if ax == 0 else ck.cols(n, a, b) for n, ax, a, b in specs]
+            w = to(torch.cat(ts, 0) if len(ts) > 1 else ts[0])
+            n_mx[2] += 1
+            n_mx[3] += w.numel() * w.element_size()
+            return w
         if native_fp8 and all(ck.is_fp8_e4m3(n) for n, *_ in specs):
             parts = [ck.fp8_part(n, ax, a, b) for n, ax, a, b in specs]
             if all(pp is not None for pp in parts) and all(
@@ -407,6 +457,10 @@ def load_hf_weights(model: LlamaModel, model_path: str):
         model.layers.append(lw)
     if n_fp8[0]:
         model.quant_linear = Q.quant_linear
+    if n_mx[0] or n_mx[2]:
+        log.info("rank %d/%d: %d projections resident as tiled MXFP4 chunks only (%.3f GiB); %d held as "
+                 "dequantised bf16 (%.3f GiB: off the GPU, or N %% 16 / K %% 256 not met)", r, W, n_mx[0],
+                 n_mx[1] / 2**30, n_mx[2], n_mx[3] / 2**30)
     if n_int4[0] or n_int4[1]:
         log.info("rank %d/%d: %d projections and %d expert stacks resident as tiled 4-bit chunks only "
                  "(INT4, %.3f GiB)", r, W, n_int4[0], n_int4[1], n_int4[2] / 2**30)
