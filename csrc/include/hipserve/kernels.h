@@ -260,6 +260,14 @@ struct PgMx {
   const float* xs;
 };
 bool launch_mxfp4_gemm(float* ws, const void* xq, const PgMx& W, int M, int N, int K, int S, hipStream_t s);
+// MXFP4 W4A8 expert GEMM (mxfp4.hip) over moe_align tiles of 16 / 32 / 64 slots: q = E experts
+// of N x K in the chunk layout above, per_e bytes apart; xq / xs of M rows, slot s reading
+// row slots[s] / gather_k (gather_k == 0: row s). glu 0: fp32 partials out [S, slots, N];
+// 1 / 2 (S == 1, rows [gate_e; up_e]): bf16 act [slots, N / 2] = silu / gelu_tanh(gate) * up.
+// (K / 256) / S in {1, 2, 3, 4, 6, 7, 8, 14, 16}.
+bool launch_mxfp4_moe_gemm(void* out, const void* xq, const float* xs, int M, const void* q, int E, long per_e,
+                           const int* slots, const int* tile_expert, int tiles_cap, int tile, int gather_k, int N,
+                           int K, int S, int glu, hipStream_t s);
 // one tiled MXFP4 part -> bf16 [N, K] rows of stride ldo (% 8) elements, exact
 bool launch_mxfp4_dequant(void* out, long ldo, const void* q, int N, int K, hipStream_t s);
 // act = silu / gelu_tanh(gate) * up of [gate | up] rows, written as per-token e4m3 q8 [rows,

@@ -215,6 +215,209 @@ bool launch_mxfp4_gemm(float* ws, const void* xq, const PgMx& W, int M, int N, i
   return mx_launch<16>(ws, x, W, M, N, K, S, s);
 }
 
+// ---- MoE experts: the same W4A8 step loop over moe_align's expert-sorted slot table.
+//   glu == 0: out[split, slot, n] = (sum over K slice of xq[row(slot), k] . w_e[n, k]) * xs[row]
+//   glu != 0: act[slot, i] = silu / gelu_tanh(gate * xs) * (up * xs), bf16, rows [gate_e; up_e]
+// q: E experts of N x K, each the tiled chunks above ([N/16][K/256][2176], per_e bytes apart).
+// Grid (128-column tiles, K slices, expert tiles of 16 MT slots): a workgroup reads its
+// tile's expert once (wave-uniform; a negative id is an unused tile of the padded table) and
+// streams that expert's chunks only. The x slice in LDS holds GATHERED rows: slot s of the
+// tile stages row slots[s] / gather_k of xq (the token of that (token, expert) pair), or row
+// s itself when gather_k == 0 (w2: its input is in slot order already). The row is resolved
+// once per thread before the K loop; a padded slot (slots[s] < 0) stages row 0 and its
+// output row is never stored.
+// GLU form: a wave owns 16 gate rows and the 16 up rows N / 2 below them — two weight
+// streams against the one x fragment, 2 MT accumulators — so the lane that holds gate
+// (m, n .. n + 3) holds up (m, n .. n + 3) too and writes four bf16 with one 8-byte store.
+// Its ring is 3 slots (two steps ahead on two streams: the 4 chunks per wave in flight of
+// the 5-slot single stream).
+template <int MT, int NSTEPS, bool GLU>
+__global__ __launch_bounds__(512) void mxfp4_moe_gemm_kernel(void* __restrict__ outp, const unsigned char* __restrict__ xq,
+                                                             const float* __restrict__ xs,
+                                                             const unsigned char* __restrict__ q, long per_e,
+                                                             const int* __restrict__ slots,
+                                                             const int* __restrict__ tile_expert, int E, int gather_k,
+                                                             int M, int N, int K, int cap, int gelu) {
+  constexpr int XR = 16 * MT;
+  constexpr int XPASS = (XR * 16 + 511) / 512;
+  constexpr int NS = GLU ? 2 : 1;                      // weight streams per wave
+  constexpr int MX_RING = GLU ? 3 : 5;
+  constexpr int AHEAD = MX_RING - 1;
+  __shared__ __attribute__((aligned(16))) unsigned char xs_lds[2][XR * MX_LDS_ROW];
+
+  const int e = tile_expert[blockIdx.z];
+  if (e < 0 || e >= E) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int split = blockIdx.y, slot0 = blockIdx.z * XR;
+  const int nsb = K >> 8;
+  const int sb0 = split * NSTEPS;
+  const int NO = GLU ? N >> 1 : N;                     // output columns the waves divide
+  const int n0 = blockIdx.x * 128 + wave * 16;
+  const bool active = n0 < NO;
+  // (idle waves of a last tile read the last 16 rows); stream 1 = the up rows, NO below
+  const unsigned char* wrow = q + (long)e * per_e + ((long)(min(n0, NO - 16) >> 4) * nsb + sb0) * MX_CHUNK;
+  const long wup = (long)(NO >> 4) * nsb * MX_CHUNK;
+
+  // the xq row of a slot; padded slots read row 0
+  auto x_row = [&](int s, int sl) { return min(gather_k > 0 ? max(sl, 0) / gather_k : s, M - 1); };
+
+  const unsigned char* xp[XPASS];
+#pragma unroll
+  for (int p = 0; p < XPASS; ++p) {
+    const int idx = p * 512 + tid;
+    xp[p] = xq;
+    if (XR * 16 % 512 == 0 || idx < XR * 16) {
+      const int s = slot0 + (idx >> 4);
+      xp[p] = xq + (long)x_row(s, slots[s]) * K + (long)sb0 * 256 + (idx & 15) * 16;
+    }
+  }
+  u32x4 xv[XPASS];
+  auto load_x = [&](int st) {
+#pragma unroll
+    for (int p = 0; p < XPASS; ++p)
+      if (XR * 16 % 512 == 0 || p * 512 + tid < XR * 16) xv[p] = *reinterpret_cast<const u32x4*>(xp[p] + st * 256);
+  };
+  auto store_x = [&](int buf) {
+#pragma unroll
+    for (int p = 0; p < XPASS; ++p) {
+      const int idx = p * 512 + tid;
+      if (XR * 16 % 512 == 0 || idx < XR * 16)
+        *reinterpret_cast<u32x4*>(&xs_lds[buf][(idx >> 4) * MX_LDS_ROW + (idx & 15) * 16]) = xv[p];
+    }
+  };
+
+  f32x4 acc[NS][MT];
+#pragma unroll
+  for (int w = 0; w < NS; ++w)
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[w][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  u32x4 ring[MX_RING][NS][2];
+  int sring[MX_RING][NS];
+  auto load_w = [&](int slot, int st) {
+#pragma unroll
+    for (int w = 0; w < NS; ++w) {
+      const unsigned char* ck = wrow + w * wup + (long)st * MX_CHUNK;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        ring[slot][w][h] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ck + h * 1024 + lane * 16));
+      sring[slot][w] = __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(ck + 2048 + lane * 2));
+    }
+  };
+
+  load_x(0);
+  store_x(0);
+  if (NSTEPS > 1) load_x(1);
+#pragma unroll
+  for (int st = 0; st < AHEAD; ++st)
+    if (st < NSTEPS) load_w(st, st);
+  __syncthreads();
+#pragma unroll
+  for (int st = 0; st < NSTEPS; ++st) {
+    if (st + 1 < NSTEPS) store_x((st + 1) % 2);
+    if (st + 2 < NSTEPS) load_x(st + 2);
+    if (st + AHEAD < NSTEPS) load_w((st + AHEAD) % MX_RING, st + AHEAD);
+    const unsigned char* xb = &xs_lds[st % 2][c * MX_LDS_ROW + g * 16];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      i32x8 a[NS];
+#pragma unroll
+      for (int w = 0; w < NS; ++w) {
+        const u32x4 w0 = ring[st % MX_RING][w][h];
+        a[w] = i32x8{(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3], 0, 0, 0, 0};
+      }
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        const u32x4 b0 = *reinterpret_cast<const u32x4*>(xb + 16 * t * MX_LDS_ROW + h * 128);
+        const u32x4 b1 = *reinterpret_cast<const u32x4*>(xb + 16 * t * MX_LDS_ROW + h * 128 + 64);
+        const i32x8 b = i32x8{(int)b0[0], (int)b0[1], (int)b0[2], (int)b0[3], (int)b1[0], (int)b1[1], (int)b1[2], (int)b1[3]};
+#pragma unroll
+        for (int w = 0; w < NS; ++w) {
+          const int sc = sring[st % MX_RING][w];
+          if (h == 0)
+            acc[w][t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[w], b, acc[w][t], 4, 0, 0, sc, 0, 127);
+          else
+            acc[w][t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[w], b, acc[w][t], 4, 0, 1, sc, 0, 127);
+        }
+      }
+    }
+#pragma unroll
+    for (int w = 0; w < NS; ++w)
+#pragma unroll
+      for (int t = 0; t < MT; ++t) asm volatile("" : "+v"(acc[w][t]));
+    if (st + 1 < NSTEPS) __syncthreads();
+  }
+
+  if (!active) return;
+  // lane: columns n = n0 + 4 g + j (j = 0..3) of slot slot0 + 16 t + c
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int s = slot0 + 16 * t + c;
+    const int sl = slots[s];
+    if (sl < 0) continue;
+    const float sx = xs[x_row(s, sl)];
+    if constexpr (GLU) {
+      float v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float gt = acc[0][t][j] * sx, up = acc[1][t][j] * sx;
+        const float y = gelu ? 1.5957691216057308f * (gt + 0.044715f * gt * gt * gt) : gt;  // common.h gelu_mul1
+        v[j] = gt / (1.f + __expf(-y)) * up;
+      }
+      *reinterpret_cast<u32x2*>(static_cast<unsigned short*>(outp) + (long)s * NO + n0 + 4 * g) =
+          u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+    } else {
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = acc[0][t][j] * sx;
+      *reinterpret_cast<f32x4*>(static_cast<float*>(outp) + ((long)split * cap + s) * N + n0 + 4 * g) = o;
+    }
+  }
+}
+
+template <int MT, bool GLU>
+static bool mx_moe_launch(void* out, const unsigned char* xq, const float* xs, const unsigned char* q, long per_e,
+                          const int* slots, const int* tile_expert, int tiles_cap, int E, int gather_k, int M, int N,
+                          int K, int S, bool gelu, hipStream_t s) {
+  const int NO = GLU ? N / 2 : N;
+  const dim3 grid((NO + 127) / 128, S, tiles_cap);
+#define MX_CASE(n)                                                                                               \
+  case n:                                                                                                        \
+    mxfp4_moe_gemm_kernel<MT, n, GLU><<<grid, 512, 0, s>>>(out, xq, xs, q, per_e, slots, tile_expert, E, gather_k, \
+                                                           M, N, K, tiles_cap * 16 * MT, gelu);               \
+    return true;
+  switch ((K >> 8) / S) {
+    MX_CASE(1) MX_CASE(2) MX_CASE(3) MX_CASE(4) MX_CASE(6) MX_CASE(7) MX_CASE(8) MX_CASE(14) MX_CASE(16)
+    default: return false;
+  }
+#undef MX_CASE
+}
+
+// tile 16 / 32 / 64 slots; (K / 256) / S in {1, 2, 3, 4, 6, 7, 8, 14, 16}; glu 0: fp32 partials
+// out [S, tiles_cap * tile, N]; 1 (SiLU) / 2 (GELU-tanh): S == 1, bf16 act [tiles_cap * tile,
+// N / 2]. xq has M rows; with gather_k == 0 at least tiles_cap * tile of them.
+bool launch_mxfp4_moe_gemm(void* out, const void* xq, const float* xs, int M, const void* q, int E, long per_e,
+                           const int* slots, const int* tile_expert, int tiles_cap, int tile, int gather_k, int N,
+                           int K, int S, int glu, hipStream_t s) {
+  if (M < 1 || E < 1 || N < 16 || N % 16 || K < 256 || K % 256 || S < 1 || (K >> 8) % S || gather_k < 0) return false;
+  if (tiles_cap < 1 || tiles_cap > 65535 || S > 65535 || (tile != 16 && tile != 32 && tile != 64)) return false;
+  if (gather_k == 0 && M < tiles_cap * tile) return false;
+  if (glu < 0 || glu > 2 || (glu && (S != 1 || (N / 2) % 16))) return false;
+  if (per_e < (long)(N >> 4) * (K >> 8) * MX_CHUNK) return false;
+  auto* x = static_cast<const unsigned char*>(xq);
+  auto* w = static_cast<const unsigned char*>(q);
+#define MX_TILE(mt)                                                                                               \
+  return glu ? mx_moe_launch<mt, true>(out, x, xs, w, per_e, slots, tile_expert, tiles_cap, E, gather_k, M, N, K, S, \
+                                       glu == 2, s)                                                               \
+             : mx_moe_launch<mt, false>(out, x, xs, w, per_e, slots, tile_expert, tiles_cap, E, gather_k, M, N, K, S, \
+                                        false, s);
+  if (tile == 16) { MX_TILE(1) }
+  if (tile == 32) { MX_TILE(2) }
+  MX_TILE(4)
+#undef MX_TILE
+}
+
 // ---- tiled chunks -> bf16 [N, K] (row stride ldo elements). Exact: an e2m1 value has one
 // mantissa bit and the scale is a power of two, so the fp32 product's low 16 bits are zero.
 // One thread per 16-byte piece (32 k of one row): 4 x 16-byte stores.

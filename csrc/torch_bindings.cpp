@@ -1185,6 +1185,40 @@ void mxfp4_gemm(at::Tensor& ws, const at::Tensor& xq, const at::Tensor& xs, cons
               "mxfp4_gemm: unsupported (M <= 256, (K / 256) / splits in the kernel's step set)");
 }
 
+// MXFP4 W4A8 expert GEMM (mxfp4.hip) over moe_align's tiles: q uint8 [E, N/16 * K/256 * 2176]
+// (each expert a tiled MXFP4 part), xq / xs the per-row e4m3 activations; slot s reads row
+// slots[s] / gather_k of xq (gather_k == 0: row s). glu 0: out fp32 [splits, slots, N]; 1 / 2:
+// expert rows [gate; up], out bf16 [slots, N / 2] = silu / gelu_tanh(gate) * up, splits == 1.
+void mxfp4_moe_gemm(at::Tensor& out, const at::Tensor& xq, const at::Tensor& xs, const at::Tensor& q, int64_t N,
+                    int64_t K, const at::Tensor& slots, const at::Tensor& tile_expert, int64_t tile, int64_t gather_k,
+                    int64_t splits, int64_t glu) {
+  Args a("mxfp4_moe_gemm", xq, "xq");
+  TORCH_CHECK(tile == 16 || tile == 32 || tile == 64, "mxfp4_moe_gemm: tile 16/32/64");
+  TORCH_CHECK(N > 0 && N % 16 == 0 && K > 0 && K % 256 == 0 && N < (1 << 24) && K < (1 << 24) && splits >= 1 &&
+              gather_k >= 0, "mxfp4_moe_gemm: N % 16, K % 256, splits >= 1, gather_k >= 0");
+  TORCH_CHECK(glu >= 0 && glu <= 2, "mxfp4_moe_gemm: glu 0 (partials), 1 (SiLU) or 2 (GELU-tanh)");
+  const void* xp = a.ptr(xq, "xq", U8, CONTIG, {at_least(1), K});
+  const int M = xq.size(0);
+  const float* xsp = a.as<float>(xs, "xs", CONTIG, exactly(M));
+  const MoeTiles t = moe_tiles(a, slots, tile_expert, tile);
+  TORCH_CHECK(t.nslots == (long)t.tiles_cap * tile, "mxfp4_moe_gemm: int32 slots [tiles * tile] and tile_expert [tiles]");
+  TORCH_CHECK(gather_k > 0 || M >= t.nslots, "mxfp4_moe_gemm: slot-indexed xq needs a row per slot");
+  const long per_e = N / 16 * (K / 256) * 2176;
+  const void* qp = a.ptr(q, "q (uint8 [E, tiled MXFP4 [N/16, K/256, 2176] expert])", U8, CONTIG, {at_least(1), per_e});
+  void* op;
+  if (glu) {
+    TORCH_CHECK(splits == 1 && (N / 2) % 16 == 0, "mxfp4_moe_gemm: the GLU form needs splits == 1 and (N / 2) % 16 == 0");
+    op = a.ptr(out, "out", BF16, CONTIG, {t.nslots, N / 2});
+  } else {
+    op = splitk_ws(a, out, splits, t.nslots, N, "out");
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(xp) % 16 == 0 && reinterpret_cast<uintptr_t>(qp) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(op) % 16 == 0, "mxfp4_moe_gemm: xq, q and out must be 16-byte aligned");
+  TORCH_CHECK(hipserve::launch_mxfp4_moe_gemm(op, xp, xsp, M, qp, (int)q.size(0), per_e, t.slots, t.tile_expert, t.tiles_cap, (int)tile,
+                                              (int)gather_k, (int)N, (int)K, (int)splits, (int)glu, cur_stream()),
+              "mxfp4_moe_gemm: unsupported ((K / 256) / splits in {1, 2, 3, 4, 6, 7, 8, 14, 16})");
+}
+
 // one tiled MXFP4 part q [N/16, K/256, 2176] -> out bf16 [N, K] (rows 16-byte aligned), exact
 void mxfp4_dequant(at::Tensor& out, const at::Tensor& q, int64_t N, int64_t K) {
   Args a("mxfp4_dequant", q, "q");
@@ -1611,6 +1645,7 @@ TORCH_LIBRARY(hipserve, m) {
   m.def("fp8_untile(Tensor(a!) out, Tensor q, int N, int K) -> ()", &fp8_untile);
   m.def("mxfp4_gemm(Tensor(a!) ws, Tensor xq, Tensor xs, Tensor[] q, int[] rows, int splits) -> ()", &mxfp4_gemm);
   m.def("mxfp4_dequant(Tensor(a!) out, Tensor q, int N, int K) -> ()", &mxfp4_dequant);
+  m.def("mxfp4_moe_gemm(Tensor(a!) out, Tensor xq, Tensor xs, Tensor q, int N, int K, Tensor slots, Tensor tile_expert, int tile, int gather_k, int splits, int glu=0) -> ()", &mxfp4_moe_gemm);
   m.def("quant_formats() -> str", &quant_formats);
   m.def("qmoe_gemm(Tensor(a!) out, Tensor(b!) ws, Tensor x, Tensor q, Tensor rs, int qtype, int N, int K, Tensor slots, Tensor tile_expert, int tile, int gather_k, int splits, bool kmajor=False, int glu=0) -> int", &qmoe_gemm);
   m.def("lora_shrink_splits(int M, int K) -> int", &lora_shrink_splits);

@@ -429,7 +429,7 @@ class LlamaModel(MoEMixin):
                 N, K = wf.shape
                 if K % 32:
                     return None, w
-                # MXFP4 (dense projections only): the uniform weights of allocate_random -> uniform
+                # MXFP4 (dense projections and experts): the uniform weights of allocate_random -> uniform
                 # codes, all 16 occurring; a block's E8M0 byte is 119..121 by its first code
                 # (mean |e2m1| 2.25 x mean scale 2^-7 x 7/6: |w| ~ 0.02)
                 u = torch.round((wf / (0.02 * math.sqrt(3.0)) + 1.0) * 7.5).clamp_(0, 15).to(torch.uint8)
@@ -476,6 +476,10 @@ class LlamaModel(MoEMixin):
         def experts(w, rowpar=False):
             parts = [q8(w[e], rowpar and not ep) for e in range(w.shape[0])]
             if all(p is not None for p, _ in parts) and Q.QuantMoE.supported(parts[0][0].kqt, *w.shape[1:]):
+                if kind == "mxfp4":  # n-major chunks for mxfp4_moe_gemm; bf16 experts with the A/B switch off
+                    if Q.mxfp4_moe_native():
+                        return Q.QuantMoE([p for p, _ in parts], kmajor=False)
+                    return torch.stack([d for _, d in parts])
                 return Q.QuantMoE([p for p, _ in parts], kmajor=not rowpar)  # w13: super-chunk major
             return torch.stack([d for _, d in parts])
 

@@ -20,7 +20,8 @@ from ..ops import quant as Q
 log = logging.getLogger(__name__)
 
 DG_MOE_STEPS = (1, 2, 3, 4, 6, 7, 8, 16)  # 256-k steps per K slice the expert decode GEMM is built for
-MOE_KERNEL_MAX_PAIRS = 2048  # larger (prefill) batches take the packed grouped GEMM (moe_grouped) ...
+MX_MOE_STEPS = (1, 2, 3, 4, 6, 7, 8, 14, 16)  # ... and the MXFP4 expert GEMM (mxfp4.hip mxfp4_moe_gemm)
+MOE_KERNEL_MAX_PAIRS = 2048 # larger (prefill) batches take the packed grouped GEMM (moe_grouped) ...
 MOE_KERNEL_MAX_ROWS_PER_EXPERT = 1024  # ... unless the streaming kernel timed faster below this (Qwen3-MoE: 128 x 768)
 
 
@@ -160,9 +161,10 @@ class MoEMixin:
         P = T * k
         hip = self.ops.name == "hip"
         if lw.w13 is not None and not isinstance(lw.w13, torch.Tensor):  # quantised experts (ops/quant.py QuantMoE)
+            mx = lw.w13.kqt == Q.MXFP4_KQT  # W4A8 expert kernel; its prefill is the dequantised bf16 route only
             if P <= MOE_KERNEL_MAX_PAIRS:
-                return self.moe_quant(x, lw, tail)
-            if (hip and self._moe_packed_shape_ok() and lw.w13.dense is None
+                return self.moe_mxfp4(x, lw, tail) if mx else self.moe_quant(x, lw, tail)
+            if (not mx and hip and self._moe_packed_shape_ok() and lw.w13.dense is None
                     and self.moe_prefill_choice(T) == "packed"):
                 # experts dequantised straight into the packed layout, then the one-launch grouped GEMMs
                 packed = (Q.moe_packed_scratch(lw.w13, 0, True), Q.moe_packed_scratch(lw.w2, 1, False))
@@ -213,11 +215,12 @@ class MoEMixin:
                 and self._moe_w2_splits(I, 1, 1) > 0)
 
     @staticmethod
-    def _moe_w2_splits(K: int, ntiles: int, active: int) -> int:
+    def _moe_w2_splits(K: int, ntiles: int, active: int, steps: tuple = DG_MOE_STEPS) -> int:
         """Split-K factor of the w2 expert GEMM: the fewest K slices (of 256 * one of
-        DG_MOE_STEPS) that give >= 1024 workgroups over the active expert tiles."""
+        ``steps``, the kernel's built step counts) that give >= 1024 workgroups over the
+        active expert tiles."""
         ks = K // 256
-        opts = sorted(ks // st for st in DG_MOE_STEPS if ks % st == 0)
+        opts = sorted(ks // st for st in steps if ks % st == 0)
         if not opts:
             return 0
         for S in opts:
@@ -433,3 +436,38 @@ class MoEMixin:
         ws = torch.empty(S, cap, H, dtype=torch.float32, device=dev)
         S = op.qmoe_gemm(out, ws, act, w2.q, w2.rs, w2.kqt, w2.N, w2.K, slots, tile_expert, tile, 0, S, w2.kmajor)
         return self._combine(out, ws[:S], S, w, pair_slot, k, tail)
+
+    def moe_mxfp4(self, x: torch.Tensor, lw, tail=None) -> torch.Tensor | None:
+        """Decode-sized MoE on MXFP4 experts (``QuantMoE`` stacks of kernel format
+        ``Q.MXFP4_KQT``) kept as their 4.25-bit chunks: routing and expert-sorted tiles as
+        ``moe_quant``, then the W4A8 expert GEMM on the scaled FP4 MFMA (mxfp4.hip
+        mxfp4_moe_gemm) against per-row e4m3 activations — w13 over the gathered token
+        rows with the GLU in its epilogue (else fp32 partials + splitk_glu), the bf16 act
+        quantised per slot, and w2 split over K into fp32 partials summed by the weighted
+        combine. Padded slots' act rows hold whatever they hold: they feed only output rows
+        no pair points at. No host synchronisation (graph-capturable)."""
+        op = torch.ops.hipserve
+        cfg = self.cfg
+        E, k, H = self.num_local_experts, cfg.num_experts_per_tok, cfg.hidden_size
+        T, dev = x.shape[0], x.device
+        P = T * k
+        tile = self._decode_tile(P)
+        w, slots, tile_expert, _, pair_slot, cap = self._route_align(x, lw, tile)
+        w13, w2 = lw.w13, lw.w2
+        I = w13.N // 2
+        gelu = cfg.hidden_act == "gelu_tanh"
+        xq, xs = pgemm.act_quant(x)
+        act = torch.empty(cap, I, dtype=x.dtype, device=dev)
+        if (w13.K // 256) in MX_MOE_STEPS and I % 16 == 0:  # one K slice: GLU in the epilogue
+            op.mxfp4_moe_gemm(act, xq, xs, w13.q, w13.N, w13.K, slots, tile_expert, tile, k, 1, 2 if gelu else 1)
+        else:
+            S13 = self._moe_w2_splits(w13.K, 1024, 1, MX_MOE_STEPS)  # the fewest slices the step set allows
+            gu = torch.empty(S13, cap, w13.N, dtype=torch.float32, device=dev)
+            op.mxfp4_moe_gemm(gu, xq, xs, w13.q, w13.N, w13.K, slots, tile_expert, tile, k, S13, 0)
+            op.splitk_glu(act, gu, S13, gelu)
+        aq, as_ = pgemm.act_quant(act)
+        active = min(E, cap // tile, P)
+        S = self._moe_w2_splits(w2.K, -(-H // 128), active, MX_MOE_STEPS)
+        ws = torch.empty(S, cap, H, dtype=torch.float32, device=dev)
+        op.mxfp4_moe_gemm(ws, aq, as_, w2.q, w2.N, w2.K, slots, tile_expert, tile, 0, S, 0)
+        return self._combine(torch.empty(T, H, dtype=x.dtype, device=dev), ws, S, w, pair_slot, k, tail)

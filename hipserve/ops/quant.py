@@ -69,6 +69,16 @@ TILED_ONLY = (G.Q2_K, G.Q3_K, G.IQ4_NL, G.IQ4_XS)
 MXFP4, MXFP4_KQT, MXFP4_CHUNK = 1005, 16, 2176
 MXFP4_TP_ERROR = ("MXFP4 weights run on one device only (tensor_parallel_size 1): the W4A8 GEMM has no "
                   "cross-rank epilogue, and dequantising every projection per decode step is no substitute")
+
+
+def mxfp4_moe_native() -> bool:
+    """MXFP4 MoE experts stay 4.25-bit ``QuantMoE`` stacks for mxfp4_moe_gemm (the default);
+    HIPSERVE_MXFP4_MOE_NATIVE=0 dequantises them to bf16 at load (the A/B switch)."""
+    import os
+
+    return os.environ.get("HIPSERVE_MXFP4_MOE_NATIVE", "1") != "0"
+
+
 BY_KQT = {f.kqt: f for f in FORMATS}  # kernel format id -> row; below: views of the table
 KERNEL_QT = {f.qtype: f.kqt for f in FORMATS}
 CHUNK_BYTES = {f.qtype: f.chunk_bytes for f in FORMATS}
@@ -1079,7 +1089,9 @@ class QuantMoE:
     for the formats whose scales sit inside the chunks). Formats (``moe`` in FORMATS): INT8 /
     INT8C (compressed-tensors 8-bit, the reference's AWQ-8bit export), INT4 (AutoAWQ gemm /
     compressed-tensors 4-bit), per-channel FP8, and the GGUF blocks (``from_blocks``: a MoE
-    GGUF's ``*_exps`` tensors stay resident as their blocks only). Prefill runs bf16 expert GEMMs on ``dense`` (a resident
+    GGUF's ``*_exps`` tensors stay resident as their blocks only). A list of MXFP4 parts
+    (kernel format ``MXFP4_KQT``, no row of the table) stacks the same way, n-major only, for
+    ``mxfp4_moe_gemm`` (mxfp4.hip) instead. Prefill runs bf16 expert GEMMs on ``dense`` (a resident
     shadow when asked for, else a per-call dequantised scratch)."""
 
     KERNEL_QTS = tuple(f.kqt for f in FORMATS if f.moe)
@@ -1087,8 +1099,13 @@ class QuantMoE:
     def __init__(self, parts: list, kmajor: bool = False):
         p0 = parts[0]
         assert all(p.kqt == p0.kqt and p.N == p0.N and p.K == p0.K and p.tiled for p in parts)
-        f = BY_KQT[p0.kqt]
-        rs = torch.stack([p.rs for p in parts]).contiguous() if f.row_scaled and f.moe else None
+        if p0.kqt == MXFP4_KQT:  # no row of the table: mxfp4_moe_gemm (mxfp4.hip), n-major chunks only
+            if kmajor:
+                raise ValueError("MXFP4 experts have no k-major layout (mxfp4_moe_gemm streams n-major chunks)")
+            rs = None
+        else:
+            f = BY_KQT[p0.kqt]
+            rs = torch.stack([p.rs for p in parts]).contiguous() if f.row_scaled and f.moe else None
         self._init(torch.stack([p.q.reshape(-1) for p in parts]).contiguous(), p0.kqt, p0.N, p0.K, rs, kmajor)
 
     def _init(self, q: torch.Tensor, kqt: int, N: int, K: int, rs, kmajor: bool):
@@ -1134,6 +1151,9 @@ class QuantMoE:
         out = out if out is not None else torch.empty(self.E, self.N, self.K, dtype=torch.bfloat16,
                                                       device=self.q.device)
         # the stacked experts [E][N/16][K/256][chunk] are one tiled [E N, K] matrix: one launch
+        if self.kqt == MXFP4_KQT:
+            torch.ops.hipserve.mxfp4_dequant(out.view(self.E * self.N, self.K), self.q.view(-1), self.E * self.N, self.K)
+            return out
         torch.ops.hipserve.gguf_dequant_tiled(out.view(self.E * self.N, self.K), self.q.view(-1),
                                               self.rs.view(-1) if self.rs.numel() else self.rs,
                                               self.kqt, self.E * self.N, self.K, 0, self.N, self.kmajor)
@@ -1143,7 +1163,10 @@ class QuantMoE:
     def supported(kqt: int, N: int, K: int, raw=None) -> bool:
         """The expert GEMM takes experts of kernel format ``kqt`` and shape [N, K]; for the
         GGUF formats with ``raw`` (their ggml blocks) also that every block scale lies in the
-        kernel's subnormal-dequant range (``sub_scale_ok``)."""
+        kernel's subnormal-dequant range (``sub_scale_ok``). MXFP4 (id 16, a key only) is
+        served by its own expert kernel, mxfp4_moe_gemm."""
+        if kqt == MXFP4_KQT:
+            return N % 16 == 0 and K % 256 == 0
         if kqt not in QuantMoE.KERNEL_QTS or N % 16 or K % 256:
             return False
         if raw is not None and kqt in GGUF_KQT:
@@ -1177,6 +1200,8 @@ def moe_packed_scratch(w: QuantMoE, slot: int, glu: bool) -> torch.Tensor:
     grouped expert GEMM (prefill_gemm_packed.hip kGroup), in a per-device scratch."""
     if w.dense is not None:
         raise ValueError("moe_packed_scratch: experts with a bf16 shadow take the shadow path")
+    if w.kqt == MXFP4_KQT:
+        raise ValueError("moe_packed_scratch: MXFP4 experts have no pack-mode dequantiser (moe_dense serves them)")
     key = (w.q.device, slot)
     n = w.E * (-(-w.N // 128) * 128) * w.K
     buf = _MOE_PACKED_SCRATCH.get(key)

@@ -336,6 +336,7 @@ def load_hf_weights(model: LlamaModel, model_path: str):
     n_fp8 = [0]
     n_int4 = [0, 0, 0]  # projections, expert stacks, resident bytes
     n_mx = [0, 0, 0, 0]  # MXFP4: projections kept, their bytes, projections held as bf16, their bytes
+    n_mxe = [0, 0]  # MXFP4 expert stacks kept as chunks, their bytes
     if ck.mxfp4 and W > 1:
         raise ValueError(Q.MXFP4_TP_ERROR)
 
@@ -445,6 +446,9 @@ def load_hf_weights(model: LlamaModel, model_path: str):
                 if getattr(w, "kqt", None) == Q.KERNEL_QT[Q.INT4]:
                     n_int4[1] += 1
                     n_int4[2] += w.q.numel()
+                if getattr(w, "kqt", None) == Q.MXFP4_KQT:
+                    n_mxe[0] += 1
+                    n_mxe[1] += w.q.numel()
         elif ck.has(p + "mlp.gate_up_proj.weight"):  # Phi-3: fused [gate; up]
             f = ck.full(p + "mlp.gate_up_proj.weight")
             I = cfg.intermediate_size
@@ -457,10 +461,11 @@ def load_hf_weights(model: LlamaModel, model_path: str):
         model.layers.append(lw)
     if n_fp8[0]:
         model.quant_linear = Q.quant_linear
-    if n_mx[0] or n_mx[2]:
-        log.info("rank %d/%d: %d projections resident as tiled MXFP4 chunks only (%.3f GiB); %d held as "
-                 "dequantised bf16 (%.3f GiB: off the GPU, or N %% 16 / K %% 256 not met)", r, W, n_mx[0],
-                 n_mx[1] / 2**30, n_mx[2], n_mx[3] / 2**30)
+    if n_mx[0] or n_mx[2] or n_mxe[0]:
+        log.info("rank %d/%d: %d projections (%.3f GiB) and %d expert stacks (%.3f GiB) resident as tiled MXFP4 "
+                 "chunks only; %d projections held as dequantised bf16 (%.3f GiB: off the GPU, or N %% 16 / "
+                 "K %% 256 not met)", r, W, n_mx[0], n_mx[1] / 2**30, n_mxe[0], n_mxe[1] / 2**30, n_mx[2],
+                 n_mx[3] / 2**30)
     if n_int4[0] or n_int4[1]:
         log.info("rank %d/%d: %d projections and %d expert stacks resident as tiled 4-bit chunks only "
                  "(INT4, %.3f GiB)", r, W, n_int4[0], n_int4[1], n_int4[2] / 2**30)
@@ -534,6 +539,25 @@ def _native_experts(ck, m, names, ex, sl, dev, int4=True):
     from ..ops import quant as Q
 
     first = f"{m}experts.{ex[0] if len(ex) else 0}.{names[0]}.weight"
+    if ck.mxfp4:
+        # Quark MXFP4 (uint8 .weight + E8M0 .weight_scale per expert): the chunks as they are,
+        # gate and up stacked by rows, for mxfp4_moe_gemm. An excluded / bf16 expert tensor or a
+        # shape off N % 16, K % 256 (from_mxfp4's ValueError) keeps the layer's experts bf16
+        tensors = [f"{m}experts.{e}.{n}.weight" for e in ex for n in names]
+        if not Q.mxfp4_moe_native() or not all(ck.is_mxfp4(t) for t in tensors):
+            return None
+        try:
+            p13, p2 = [], []
+            for e in ex:
+                g, u, d = (ck.mxfp4_part(f"{m}experts.{e}.{n}.weight", ax, sl.start, sl.stop)
+                           for n, ax in zip(names, (0, 0, 1)))
+                if d is None:
+                    return None
+                p13.append(Q.QuantPart.from_mxfp4(torch.cat([g[0], u[0]]), torch.cat([g[1], u[1]]), dev))
+                p2.append(Q.QuantPart.from_mxfp4(d[0], d[1], dev))
+        except ValueError:
+            return None
+        return Q.QuantMoE(p13), Q.QuantMoE(p2)
     int8 = ck.is_int8_ct(first)
     i4 = int4 and not int8 and ck.is_int4(first)
     if not int8 and not i4 and not ck.is_fp8_e4m3(first):
