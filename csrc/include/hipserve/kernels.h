@@ -61,6 +61,9 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
                               const int* tiles, int ntiles, int nq, int nkv, int D,
                               int block_size, float scale, int window, hipStream_t s, bool kv_f8 = false,
                               float softcap = 0.f, const int* limits = nullptr);
+// the kernel the launcher takes for this shape: 2 = LDS-shared K / V tiles (v2 at head_dim 128,
+// its one-wave-per-SIMD form at 256), 1 = v1; honours HIPSERVE_PREFILL_ATTN_V1 as the launcher does
+int prefill_attention_variant(int D, int nq, int nkv, int block_size, int bt_stride);
 
 // sampling.hip
 // ws: fp32 workspace of sample_workspace_floats(rows, V) for the multi-CU path

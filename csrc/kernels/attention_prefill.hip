@@ -15,6 +15,8 @@
 //    lane movement (accumulator-as-operand, guide §3); the matching A operand is
 //    V^T, which the transposed-per-block V cache serves as two 8-byte loads.
 //  * online softmax in the log2 domain.
+// Below it: v2 (LDS-shared K/V tiles, head_dim 128) and its one-wave-per-SIMD counterpart at
+// head_dim 256; prefill_attention_variant() is the launcher's choice between them and v1.
 #include <cstdlib>
 
 #include <type_traits>
@@ -211,11 +213,6 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(
 //  * LDS rows padded (K 272 B, V^T 144 B): the 16 lanes of each b128 read phase
 //    hit 16 distinct 16-byte bank groups.
 //  * heaviest query tiles are dispatched first against the causal tail.
-static bool getenv_flag(const char* name) {
-  const char* e = getenv(name);
-  return e != nullptr && *e != 0 && *e != '0';
-}
-
 constexpr int PA2_KT = 64, PA2_KLD = 128 + 8, PA2_VLD = 64 + 8;
 
 // (A stagger — waves 4-7 issuing each tile's P.V one tile late, a third LDS buffer holding
@@ -487,6 +484,330 @@ __global__ __launch_bounds__(64 * NWV) void prefill_attn_v2_kernel(
   }
 }
 
+// ---- LDS-shared K/V tiles at head_dim 256 (Gemma-2 / Gemma-3), G = nq/nkv >= 2 ----
+//
+// v2's contract (HG query heads of one kv head x blocks of 32 query rows per workgroup, every
+// 64-key K / V tile loaded into LDS once, S^T / O^T on the 32x32x16 MFMA with the swapped K
+// rows, log2-domain softmax with the lazy rescale, masks on edge tiles only, block ids staged in
+// LDS, e4m3 widened on the way into LDS) on a plan of its own, because neither of v2's budgets
+// holds at D = 256:
+//  * registers: Q 64 + O^T 128 + two S sets 64 + staging = over the 256 of two waves per SIMD
+//    by far, inside the unified 512-entry VGPR + AGPR file of ONE wave per SIMD. So 4-wave
+//    workgroups (the plan the d256 decode kernel took), HG = min(G, 4): G = 2 -> 2 heads x 2
+//    row blocks (64 query rows), G >= 4 -> 4 heads x 32 rows. (The 8-wave / 32-key-tile
+//    alternative leaves 48 registers next to Q and O for S, P, staging, fragments, addresses.)
+//  * LDS: a 64-key tile is 33 KiB of K (528 B rows) + 36 KiB of V^T (144 B rows); the ring of
+//    two is 138 KiB of the CU's 160: one workgroup per CU, 20 KiB left for the block ids.
+//  * with one wave on a SIMD no partner wave hides the softmax VALU behind its MFMAs (v2's
+//    4-wave form: 2.5-2.8x slower than its 8-wave form), so the wave pipelines itself: the 32
+//    QK MFMAs of tile t+1 (second S accumulator set) are issued k-step by k-step around tile
+//    t's mask / max / exp2 VALU, then tile t's 32 P.V MFMAs run back to back.
+//  * that skew splits the ring: in iteration t the workgroup reads K(t+1) and V(t), so K is
+//    staged two tiles ahead and V^T one, into the K buffer of tile t and the V buffer of tile
+//    t-1, both dead since the last barrier: still one barrier per tile.
+//  * ONE staging register set of 8 pieces per thread, used twice per iteration: K(t+2) is
+//    issued before the QK + softmax half and written to LDS after it, V^T(t+1) is issued then
+//    and written after the P.V half. v2's two sets (loads two tiles ahead) and a per-wave
+//    choice of QK-only / softmax-only bodies were tried first and spilled 480-712 bytes per
+//    lane; so every wave runs every tile of the workgroup's range in one straight-line body.
+// Resource lines: profiles/attn_d256_v2_resources.md (every instantiation: scratch 0).
+constexpr int PA256_KLD = 256 + 8;
+constexpr size_t PA256_BT_LDS = 20 * 1024;  // dynamic LDS for block ids next to the 138 KiB ring
+
+template <int HG, typename KV, bool kCap = false, bool kLim = false>
+__global__ __launch_bounds__(256) void prefill_attn_d256_kernel(
+    unsigned short* __restrict__ out, long out_stride, const unsigned short* __restrict__ q, long q_stride,
+    const KV* __restrict__ k_cache, const KV* __restrict__ v_cache,
+    const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ cu_q,
+    const int* __restrict__ ctx_lens, const int* __restrict__ tiles, int nq, int nkv, int block_size,
+    float scale, int window, int prio, float softcap, const int* __restrict__ limits) {
+  constexpr int D = 256, KS = 16, NB = 8, NWV = 4, NT = 64 * NWV;
+  constexpr int RB = NWV / HG, QR = 32 * RB, SUB = 128 / QR;
+  constexpr int NP = PA2_KT * D / 8 / NT;  // 8 K pieces and 8 V^T pieces of 16 B per thread per tile
+  __shared__ __attribute__((aligned(16))) unsigned short kl[2][PA2_KT * PA256_KLD];
+  __shared__ __attribute__((aligned(16))) unsigned short vl[2][D * PA2_VLD];
+
+  // v2's dispatch order: kv-head group fastest, host tile, heavier sub-tile first
+  const int L = blockIdx.x + gridDim.x * blockIdx.y, gy = gridDim.y;
+  const int gyi = L % gy, rest = L / gy;
+  const int t = rest / SUB, sub = SUB - 1 - (rest - t * SUB);
+  const int seq = tiles[2 * t], r0 = tiles[2 * t + 1] + sub * QR;
+  const int q0 = cu_q[seq], qlen = cu_q[seq + 1] - q0;
+  if (r0 >= qlen) return;  // whole workgroup: before any barrier
+  const int ctx = ctx_lens[seq];
+  const int G = nq / nkv;
+  const int kh = gyi / (G / HG);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int hs = wave % HG, rb = wave / HG;
+  const int h = gyi * HG + hs;
+  const int qi = lane & 31, half = lane >> 5;
+  const int wrow0 = r0 + rb * 32;
+  const bool wactive = wrow0 < qlen;
+  const int row = min(wrow0 + qi, qlen - 1);
+  const int pos = ctx - qlen + row;
+  const int wmax_key = ctx - qlen + min(wrow0 + 31, qlen - 1);
+  const int wmin_pos = ctx - qlen + wrow0;
+  int nkt = (ctx - qlen + min(r0 + QR - 1, qlen - 1)) / PA2_KT + 1;
+  // limits (kLim): this row's last key and the workgroup's (its last row's)
+  int lim_pos = pos;
+  if constexpr (kLim) {
+    lim_pos = min(max(pos, limits[q0 + row]), ctx - 1);
+    nkt = min(max(nkt * PA2_KT - 1, limits[q0 + min(r0 + QR - 1, qlen - 1)]), ctx - 1) / PA2_KT + 1;
+  }
+  // sliding window: the workgroup starts at the tile of its first row's lowest key
+  const int kt0 = window > 0 ? max(0, ctx - qlen + r0 - window + 1) / PA2_KT : 0;
+  const int* btab = block_tables + (long)seq * bt_stride;
+  const long hstride = (long)block_size * D;
+  const int bsh = __builtin_ctz(block_size), bmask = block_size - 1;
+  extern __shared__ int bts[];
+  const int blk_lo = (kt0 * PA2_KT) >> bsh, blk_hi = (min(nkt * PA2_KT, ctx) - 1) >> bsh;
+  for (int i = tid; i <= blk_hi - blk_lo; i += NT) bts[i] = btab[blk_lo + i];
+  __syncthreads();
+
+  using KV8 = typename KvVec<KV>::T;
+  KV8 sx[NP];  // the one staging set: K(kt + 2) around QK + softmax, then V^T(kt + 1) around P.V
+  const unsigned blk_elems = (unsigned)(nkv * hstride);
+  const KV* kc_h = k_cache + (long)kh * hstride;
+  const KV* vc_h = v_cache + (long)kh * hstride;
+  // Staging pieces of thread tid, written out per piece so that every per-piece term is a
+  // compile-time constant (hoisted per-piece address registers were what spilled):
+  //  K piece i (p = tid + 256 i): key kbase + k0 + 8 i, 16-byte column kc8 / 8 (a key row is 512 B)
+  //  V^T piece i: row vd0 + 128 (i & 1), keys 16 (i >> 1) + vk8 .. + 7 of the tile
+  const int k0 = tid >> 5, kc8 = (tid & 31) * 8, vd0 = tid >> 1, vk8 = 8 * (tid & 1);
+  // LDS K rows have key bits 2 and 3 swapped: bit 2 of k0 -> row bit 3, bit 0 of i -> row bit 2
+  unsigned short* const kst = &kl[0][((k0 & 3) | ((k0 & 4) << 1)) * PA256_KLD + kc8];
+  unsigned short* const vst = &vl[0][vd0 * PA2_VLD + vk8];
+  auto load_k = [&](KV8(&sk)[NP], int kt) __attribute__((always_inline)) {
+    const int kbase = kt * PA2_KT + k0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int key = min(kbase + 8 * i, ctx - 1);
+      const unsigned kid = (unsigned)bts[(key >> bsh) - blk_lo];
+      sk[i] = kv_load8(kc_h + ((unsigned long)kid * blk_elems + (unsigned)((key & bmask) * D + kc8)));
+    }
+  };
+  auto load_v = [&](KV8(&sv)[NP], int kt) __attribute__((always_inline)) {
+    const int kbase = kt * PA2_KT + vk8;
+#pragma unroll
+    for (int j = 0; j < NP / 2; ++j) {  // one block lookup per 16-key group, two rows 128 apart
+      int vkey = kbase + 16 * j;
+      if (vkey > ctx - 1) vkey = (ctx - 1) & ~7;
+      const unsigned vid = (unsigned)bts[(vkey >> bsh) - blk_lo];
+      const KV* vp = vc_h + ((unsigned long)vid * blk_elems + (unsigned)(vd0 * block_size + (vkey & bmask)));
+      sv[2 * j] = kv_load8(vp);
+      sv[2 * j + 1] = kv_load8(vp + 128 * block_size);
+    }
+  };
+  auto store_k = [&](const KV8(&sk)[NP], int buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+      *reinterpret_cast<u16x8*>(kst + (buf * PA2_KT + (((i & 1) << 2) | ((i >> 1) << 4))) * PA256_KLD) =
+          kv_widen8(sk[i]);
+  };
+  auto store_v = [&](const KV8(&sv)[NP], int buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+      *reinterpret_cast<u16x8*>(vst + (buf * D + 128 * (i & 1)) * PA2_VLD + 16 * (i >> 1)) = kv_widen8(sv[i]);
+  };
+
+  bf16x8 qf[KS];
+  {
+    const unsigned short* qp = q + (long)(q0 + row) * q_stride + (long)h * D + 8 * half;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+      qf[ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(qp + 16 * ks));
+  }
+  const float sl2 = scale * 1.4426950408889634f;
+  [[maybe_unused]] const SoftCap cap = softcap_make(kCap ? softcap : 1.f, scale, 1.4426950408889634f);
+  f32x16 o[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[nb][r] = 0.f;
+  float m_run = -1e30f, l_run = 0.f;
+
+  // One pipeline step of a wave. QK: sn = K(kt + 1) . Q^T from K buffer vb ^ 1. SM: softmax of
+  // sc = the raw scores of tile kt, then O^T += V^T(kt) . P^T from V buffer vb. With both, the
+  // softmax VALU is dealt over the k-steps of QK: masks / cap / max on k-steps 0-3, the row max
+  // and the lazy rescale on 4, four exp2 per k-step on 5-12 (kCap: 0-7, 8, eight per k-step on 9-12).
+  auto step = [&](auto qk_c, auto sm_c, f32x16(&sc)[2], f32x16(&sn)[2], int kt, int vb) __attribute__((always_inline)) {
+    constexpr bool QK = decltype(qk_c)::value, SM = decltype(sm_c)::value;
+    const int kbase = kt * PA2_KT;
+    const unsigned short* kb = &kl[vb ^ 1][qi * PA256_KLD + 8 * half];
+    u16x8 kf[2][2];
+    if constexpr (QK) {
+#pragma unroll
+      for (int h2 = 0; h2 < 2; ++h2) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sn[h2][r] = 0.f;
+        kf[0][h2] = *reinterpret_cast<const u16x8*>(kb + (32 * h2) * PA256_KLD);
+      }
+    }
+    // edge tile: the diagonal (or the limit's reach) or some row's window start
+    const bool edge = SM && (kbase + PA2_KT - 1 > wmin_pos || (window > 0 && kbase <= wmax_key - window));
+    const int lim = lim_pos - kbase - 8 * half;  // slot offset > lim: a hidden (future) key
+    // slot offset <= lo: before the window (which hangs on pos, not on the limit)
+    const int lo = window > 0 ? pos - kbase - 8 * half - window : -PA2_KT;
+    float mx = -1e30f;
+    float ps[4] = {0.f, 0.f, 0.f, 0.f};
+    bf16x8 pb[2][2];
+    if (prio) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      if constexpr (QK) {
+        if (ks + 1 < KS) {
+#pragma unroll
+          for (int h2 = 0; h2 < 2; ++h2)
+            kf[(ks + 1) & 1][h2] = *reinterpret_cast<const u16x8*>(kb + (32 * h2) * PA256_KLD + 16 * (ks + 1));
+        }
+        __builtin_amdgcn_sched_barrier(0);  // the reads of k-step ks + 1 stay ahead of k-step ks's MFMAs
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+          sn[h2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[ks & 1][h2]), qf[ks], sn[h2],
+                                                           0, 0, 0);
+      }
+      if constexpr (SM) {
+        // the cap's exp2 + rcp per score take twice the k-steps for the first phase
+        constexpr int MS = kCap ? 8 : 4, MC = 32 / MS, EC = kCap ? 8 : 4;
+        if (ks < MS) {  // MC scores: cap (before every mask), masks on edge tiles, running max
+          const int h2 = ks / (MS / 2), rlo = MC * (ks % (MS / 2));
+          if constexpr (kCap) {
+#pragma unroll
+            for (int r = rlo; r < rlo + MC; ++r) sc[h2][r] = softcap_apply(sc[h2][r], cap);
+          }
+          if (edge) {
+#pragma unroll
+            for (int r = rlo; r < rlo + MC; ++r) {
+              const int off = 32 * h2 + 16 * (r >> 3) + (r & 7);
+              if (off > lim || off <= lo) sc[h2][r] = -INFINITY;
+            }
+          }
+#pragma unroll
+          for (int r = rlo; r < rlo + MC; ++r) mx = fmaxf(mx, sc[h2][r]);
+        } else if (ks == MS) {
+          mx = xor32_max(mx);
+          const float m_new = fmaxf(m_run, kCap ? mx : mx * sl2);
+          // lazy rescale (v2): keep the running max while no row's max grew by more than 8
+          if (!__all(m_new - m_run <= 8.f)) {
+            const float alpha = exp2f(m_run - m_new);
+            l_run *= alpha;
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) o[nb][r] *= alpha;
+            m_run = m_new;
+          }
+        } else if (ks < 13) {  // EC probabilities
+          const int c = ks - (MS + 1), h2 = c / (16 / EC), rlo = EC * (c % (16 / EC));
+#pragma unroll
+          for (int r = rlo; r < rlo + EC; ++r) {
+            float p;
+            if constexpr (kCap) p = __builtin_amdgcn_exp2f(sc[h2][r] - m_run);
+            else p = __builtin_amdgcn_exp2f(fmaf(sc[h2][r], sl2, -m_run));
+            ps[r & 3] += p;
+            pb[h2][r >> 3][r & 7] = static_cast<__bf16>(p);
+          }
+        }
+      }
+      if constexpr (QK) __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (SM) {
+      // staging, first half: K(kt + 2) into the K buffer that held K(kt), then V^T(kt + 1) issued
+      if (kt + 2 < nkt) store_k(sx, vb);
+      if (kt + 1 < nkt) load_v(sx, kt + 1);
+      // 8 groups of 4 MFMAs (k-slot group g / 2, d blocks 4 (g & 1) ..): the V^T fragments of
+      // group g + 1 are read ahead of group g's MFMAs, two fragment sets of 16 registers
+      const unsigned short* vp = &vl[vb][qi * PA2_VLD + 8 * half];
+      u16x8 vf[2][4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) vf[0][j] = *reinterpret_cast<const u16x8*>(vp + 32 * j * PA2_VLD);
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        if (g + 1 < 8) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            vf[(g + 1) & 1][j] = *reinterpret_cast<const u16x8*>(vp + 16 * ((g + 1) >> 1) +
+                                                                  32 * (4 * ((g + 1) & 1) + j) * PA2_VLD);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o[4 * (g & 1) + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[g & 1][j]),
+                                                                       pb[g >> 2][(g >> 1) & 1], o[4 * (g & 1) + j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      l_run += (ps[0] + ps[1]) + (ps[2] + ps[3]);
+      if (kt + 1 < nkt) store_v(sx, vb ^ 1);  // second half: into the V buffer that held V^T(kt - 1)
+    }
+    if (prio) __builtin_amdgcn_s_setprio(0);
+  };
+  // Every wave runs every tile of the workgroup's range [kt0, nkt): a wave's own range is at most
+  // one tile shorter at either end (QR <= 64 rows), and those tiles are edge tiles that mask to
+  // p = 0 for all of its rows. One straight-line body per buffer parity keeps the 192 accumulators
+  // where they are; the last iteration's QK reads a stale K buffer into scores nobody uses.
+  // prologue: K(kt0) -> K buffer 0, V(kt0) -> V buffer 0, K(kt0 + 1) -> K buffer 1, one round trip
+  {
+    KV8 pk[NP], pv[NP];
+    load_k(pk, kt0);
+    load_v(pv, kt0);
+    if (kt0 + 1 < nkt) load_k(sx, kt0 + 1);
+    store_k(pk, 0);
+    store_v(pv, 0);
+    if (kt0 + 1 < nkt) store_k(sx, 1);
+  }
+  __syncthreads();
+  f32x16 sa[2], sb[2];
+  step(std::true_type{}, std::false_type{}, sb, sa, kt0 - 1, 1);  // S(kt0)
+  for (int kt = kt0; kt < nkt; kt += 2) {
+    // S(kt) in sa, K(kt + 1) in K buffer 1, V(kt) in V buffer 0
+    if (kt + 2 < nkt) load_k(sx, kt + 2);
+    step(std::true_type{}, std::true_type{}, sa, sb, kt, 0);
+    __syncthreads();
+    if (kt + 1 >= nkt) break;
+    // S(kt + 1) in sb, K(kt + 2) in K buffer 0, V(kt + 1) in V buffer 1
+    if (kt + 3 < nkt) load_k(sx, kt + 3);
+    step(std::true_type{}, std::true_type{}, sb, sa, kt + 1, 1);
+    __syncthreads();
+  }
+  if (!wactive) return;
+  l_run = xor32_sum(l_run);
+  const float inv = 1.f / l_run;
+  if (wrow0 + qi < qlen) {
+    unsigned short* op = out + (long)(q0 + wrow0 + qi) * out_stride + (long)h * D;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        u16x4v w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = f32_to_bf16(o[nb][4 * g + j] * inv);
+        *reinterpret_cast<u16x4v*>(op + 32 * nb + 8 * g + 4 * half) = w;
+      }
+  }
+}
+
+static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+// Unset HIPSERVE_PREFILL_ATTN_V1 takes the LDS-shared kernel at head_dim 256 (measured against
+// v1 in profiles/attn_d256_v2_bench.log)
+constexpr bool kD256SharedByDefault = true;
+
+// 2: the LDS-shared kernel (v2 at 128, prefill_attn_d256_kernel at 256), 1: v1. The launcher's
+// own choice, exported as the op prefill_attention_variant.
+int prefill_attention_variant(int D, int nq, int nkv, int block_size, int bt_stride) {
+  const char* e = getenv("HIPSERVE_PREFILL_ATTN_V1");
+  const bool unset = e == nullptr || *e == 0;
+  if (!unset && *e != '0') return 1;  // forced v1
+  if (nkv <= 0 || nq % nkv != 0) return 1;  // no head layout (the binding refuses it before the launcher)
+  const int G = nq / nkv;
+  if (block_size % 16 != 0 || !pow2(block_size) || G < 2 || !pow2(G)) return 1;
+  // the sequence's block ids sit in LDS next to the K / V ring (160 KiB per CU): 70 KiB at 128, 138 at 256
+  const size_t bt_lds = (size_t)bt_stride * sizeof(int);
+  if (D == 128) return bt_lds <= 64 * 1024 ? 2 : 1;
+  if (D == 256) return bt_lds <= PA256_BT_LDS && (!unset || kD256SharedByDefault) ? 2 : 1;
+  return 1;
+}
+
 void launch_prefill_attention(void* out, long out_stride, const void* q,
                               long q_stride, const void* k_cache,
                               const void* v_cache, const int* block_tables,
@@ -496,19 +817,52 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
                               const int* limits) {
   if (ntiles <= 0) return;
   const int G = nq / nkv;
-  // v2 keeps the sequence's block ids in LDS next to its 70 KiB K / V ring (160 KiB per CU)
-  if (D == 128 && block_size % 16 == 0 && (block_size & (block_size - 1)) == 0 && G >= 2 && (G & (G - 1)) == 0 &&
-      (size_t)bt_stride * sizeof(int) <= 64 * 1024 &&
-      !getenv_flag("HIPSERVE_PREFILL_ATTN_V1")) {
+  const bool shared = prefill_attention_variant(D, nq, nkv, block_size, bt_stride) == 2;
+  // s_setprio 1 around each MFMA cluster; HIPSERVE_PREFILL_ATTN_PRIO=0 turns it off
+  const char* ep = getenv("HIPSERVE_PREFILL_ATTN_PRIO");
+  const int prio = ep != nullptr && atoi(ep) == 0 ? 0 : 1;
+  if (shared && D == 256) {
+    const int HG = G >= 4 ? 4 : 2;
+    dim3 g3(ntiles * (HG == 4 ? 4 : 2), nkv * (G / HG));
+    const size_t bt_lds = (size_t)bt_stride * sizeof(int);
+    // static 138 KiB ring + the block ids: above the 64 KiB default (160 KiB per CU)
+#define PA256_GO(hg, KVT, CAP, LIM)                                                                                \
+  do {                                                                                                             \
+    static bool attr = [] {                                                                                        \
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_attn_d256_kernel<hg, KVT, CAP, LIM>),      \
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)PA256_BT_LDS) == hipSuccess;     \
+    }();                                                                                                           \
+    (void)attr;                                                                                                    \
+    prefill_attn_d256_kernel<hg, KVT, CAP, LIM><<<g3, 256, bt_lds, s>>>(                                           \
+        static_cast<unsigned short*>(out), out_stride, static_cast<const unsigned short*>(q), q_stride,            \
+        static_cast<const KVT*>(k_cache), static_cast<const KVT*>(v_cache), block_tables, bt_stride, cu_q,         \
+        ctx_lens, tiles, nq, nkv, block_size, scale, window, prio, softcap, limits);                               \
+  } while (0)
+#define PA256_KV(hg, CAP, LIM)                                                                                     \
+  do {                                                                                                             \
+    if (kv_f8) PA256_GO(hg, unsigned char, CAP, LIM);                                                              \
+    else PA256_GO(hg, unsigned short, CAP, LIM);                                                                   \
+  } while (0)
+#define PA256_LAUNCH(hg)                                                                                           \
+  do {                                                                                                             \
+    if (limits != nullptr) PA256_KV(hg, false, true); /* no soft-capping with limits (the binding refuses it) */   \
+    else if (softcap > 0.f) PA256_KV(hg, true, false);                                                             \
+    else PA256_KV(hg, false, false);                                                                               \
+  } while (0)
+    if (HG == 4) PA256_LAUNCH(4);
+    else PA256_LAUNCH(2);
+#undef PA256_LAUNCH
+#undef PA256_KV
+#undef PA256_GO
+    return;
+  }
+  if (shared) {  // D == 128: v2
     const char* ew = getenv("HIPSERVE_PREFILL_ATTN_WAVES");  // 8 (default) or 4 waves per workgroup
     const int nwv = (ew != nullptr && atoi(ew) == 4) ? 4 : 8;
     const int HG = G >= nwv ? nwv : G;
-    // s_setprio 1 around each MFMA cluster (the partner wave's softmax VALU yields to it):
-    // 3 % faster at 1K-32K tokens (profiles/r4_prefill_attn_setprio.log; a static
-    // priority for the younger wave of each SIMD gained 1 %); HIPSERVE_PREFILL_ATTN_PRIO=0
-    // turns it off
-    const char* ep = getenv("HIPSERVE_PREFILL_ATTN_PRIO");
-    const int prio = ep != nullptr && atoi(ep) == 0 ? 0 : 1;
+    // prio (the partner wave's softmax VALU yields to the MFMA cluster): 3 % faster at 1K-32K
+    // tokens (profiles/r4_prefill_attn_setprio.log; a static priority for the younger wave of
+    // each SIMD gained 1 %)
     const int sub = 128 / (32 * (nwv / HG));
     dim3 g2(ntiles * sub, nkv * (G / HG));
     auto* o2 = static_cast<unsigned short*>(out);
@@ -608,8 +962,8 @@ void launch_prefill_attention(void* out, long out_stride, const void* q,
     else PA1_LAUNCH_LIM(128);
     return;
   }
-  // head_dim 256 (Gemma-3 1B / 4B / 12B) runs v1: 256 VGPRs + the accumulators in AGPRs at one
-  // wave per SIMD, no scratch; a v2-class kernel there is a design of its own (README Limits)
+  // head_dim 256 on v1 (G = 1, other G, a long block table, HIPSERVE_PREFILL_ATTN_V1=1): 256 VGPRs
+  // + the accumulators in AGPRs at one wave per SIMD, no scratch
   if (D == 256) PA1_LAUNCH(256);
   else if (D == 128) PA1_LAUNCH(128);
   else if (D == 96) PA1_LAUNCH(96);

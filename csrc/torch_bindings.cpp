@@ -545,6 +545,10 @@ void prefill_attention(at::Tensor& out, const at::Tensor& q, const at::Tensor& k
                                      kv.f8, (float)softcap, lp);
 }
 
+int64_t prefill_attention_variant(int64_t head_dim, int64_t nq, int64_t nkv, int64_t block_size, int64_t bt_stride) {
+  return hipserve::prefill_attention_variant((int)head_dim, (int)nq, (int)nkv, (int)block_size, (int)bt_stride);
+}
+
 // Per-head RMSNorm of q and k inside the merged qkv rows, in place (Qwen3 / Gemma-3).
 void qk_rmsnorm(at::Tensor& qkv, const at::Tensor& q_w, const at::Tensor& k_w, int64_t nq, int64_t nkv,
                 int64_t head_dim, double eps) {
@@ -1649,6 +1653,7 @@ TORCH_LIBRARY(hipserve, m) {
   m.def("quant_formats() -> str", &quant_formats);
   m.def("qmoe_gemm(Tensor(a!) out, Tensor(b!) ws, Tensor x, Tensor q, Tensor rs, int qtype, int N, int K, Tensor slots, Tensor tile_expert, int tile, int gather_k, int splits, bool kmajor=False, int glu=0) -> int", &qmoe_gemm);
   m.def("lora_shrink_splits(int M, int K) -> int", &lora_shrink_splits);
+  m.def("prefill_attention_variant(int head_dim, int nq, int nkv, int block_size, int bt_stride) -> int", &prefill_attention_variant);
   m.def("stage_copy(Tensor(a!)[] dst, Tensor[] src, int device) -> ()", &stage_copy);
   m.def("car_create(int rank, int world, int max_bytes, int nb_large=512) -> int", &car_create);
   m.def("car_handle(int state) -> Tensor", &car_handle);

@@ -149,7 +149,7 @@ def bench_decode(ops):
 
 
 def bench_prefill(ops):
-    D, bs = int(os.environ.get("BENCH_D", "128")), 16  # head_dim 256 runs v1 whatever the version asked for
+    D, bs = int(os.environ.get("BENCH_D", "128")), 16
     shapes = [(1024, 8, 32, 8), (4096, 2, 32, 8), (8192, 1, 32, 8), (1024, 8, 8, 1)]
     if os.environ.get("BENCH_PREFILL_LONG"):
         shapes = [(1024, 8, 32, 8), (8192, 1, 32, 8), (32768, 1, 32, 8)]
@@ -172,11 +172,15 @@ def bench_prefill(ops):
         for ver in vers:  # v1: per-wave L2 K/V reads (HIPSERVE_PREFILL_ATTN_V1=1)
             os.environ["HIPSERVE_PREFILL_ATTN_V1"] = "1" if ver == "v1" else "0"
             os.environ["HIPSERVE_PREFILL_ATTN_WAVES"] = "8" if ver == "v2w8" else "4"
+            # the kernel the launcher takes for this shape under that setting (1 = v1, 2 = LDS-shared
+            # K / V tiles; HIPSERVE_PREFILL_ATTN_WAVES does not apply at head_dim 256)
+            kern = torch.ops.hipserve.prefill_attention_variant(D, nq, nkv, bs, bt.stride(0))
             for cap in softcaps():
                 us = timeit(lambda: ops.prefill_attention(out, q, kc, vc, bt, cu, ctx, tiles, nq, nkv,
                                                           1 / math.sqrt(D), 0, cap), n=10)
-                emit(op="prefill_attention", D=D, ver=ver, kv="fp8" if kvt == torch.float8_e4m3fn else "bf16", S=S,
-                     nseq=nseq, nq=nq, nkv=nkv, softcap=cap, us=round(us, 1), TFLOPs=round(flops / us / 1e6, 1))
+                emit(op="prefill_attention", D=D, ver=ver, kernel=kern,
+                     kv="fp8" if kvt == torch.float8_e4m3fn else "bf16", S=S, nseq=nseq, nq=nq, nkv=nkv, softcap=cap,
+                     us=round(us, 1), TFLOPs=round(flops / us / 1e6, 1))
             # BENCH_LIMITS=1: the per-row key limit kernels too (Gemma-3 image blocks), on the same
             # tensors: one 256-token block per sequence at rows [S/2, S/2 + 256), and limits equal
             # to every row's own position ("own": the limit kernel doing the causal kernel's work)
@@ -187,8 +191,9 @@ def bench_prefill(ops):
                 for name, lim in (("own", own), ("block256", blk.view(-1))):
                     us = timeit(lambda: ops.prefill_attention(out, q, kc, vc, bt, cu, ctx, tiles, nq, nkv,
                                                               1 / math.sqrt(D), 0, 0.0, lim), n=10)
-                    emit(op="prefill_attention", D=D, ver=ver, kv="fp8" if kvt == torch.float8_e4m3fn else "bf16",
-                         S=S, nseq=nseq, nq=nq, nkv=nkv, limits=name, us=round(us, 1),
+                    emit(op="prefill_attention", D=D, ver=ver, kernel=kern,
+                         kv="fp8" if kvt == torch.float8_e4m3fn else "bf16", S=S, nseq=nseq, nq=nq, nkv=nkv,
+                         limits=name, us=round(us, 1),
                          TFLOPs=round(flops / us / 1e6, 1))
         os.environ.pop("HIPSERVE_PREFILL_ATTN_V1", None)
 
